@@ -12,7 +12,9 @@ exchange step); each rank scores its query shard against the full gallery; per-q
 results are all-gathered and rank 0 reduces them in query order (bit-identical to N=1).
 Total work is fixed as N grows ("strong").
 
-Extra legs in the same JSON line (not part of `value`): "msmt17" = configs[3] / the north
+A plain run sets up, warms up, times the steps and prints the result line of the Market step
+alone.  `--full` adds the extra legs to the same JSON line (not part of `value`; each can be
+switched off again with its `--no-*`): "msmt17" = configs[3] / the north
 star's target, MSMT17 end to end on all ranks (sharded embed, all-gather, distmat + CMC/mAP,
 sharded k-reciprocal re-rank + CMC/mAP, wall seconds max over ranks); "rerank" = configs[2]'s
 Duke-size re-rank on rank 0 with the C port timed on the full config; "text" = the --mm
@@ -23,7 +25,11 @@ the same Market eval from 19 281 host JPEG buffers through get_loader -> inferen
 get_cmc_map (N = 1); "cpu_baseline".
 
     python bench.py [--gpus N] [--steps K] [--warmup W] [--batch B (default 20480)] [--backend nccl|gloo]
-                    [--no-cpu-baseline] [--no-rerank] [--no-msmt17] [--no-text] [--no-jpeg] [--no-files]
+                    [--dump-outputs DIR]
+                    [--full [--no-cpu-baseline] [--no-rerank] [--no-msmt17] [--no-text] [--no-jpeg] [--no-files]
+                            [--no-backend] [--no-preprocess]]
+
+`--dump-outputs DIR` writes what the last timed step computed as DIR/<name>.npy (dump_outputs).
 
 `--gpus N` under torchrun (WORLD_SIZE set) must equal the world size; without torchrun,
 bench.py starts the N rank processes itself (launch_ranks) and relays rank 0's line.
@@ -212,7 +218,8 @@ class Workload:
     def step(self):
         """One Market eval; returns (cmc, mAP, embed s, all-gather s, eval s) of this rank.  The
         all-gather of the normalised gallery blocks (RCCL under nccl) is timed on its own: it
-        includes waiting for the slowest rank, so its minimum over ranks is the collective."""
+        includes waiting for the slowest rank, so its minimum over ranks is the collective.
+        The step's arrays stay in self.emb / self.dist / self.rows until the next step."""
         t0 = time.perf_counter()
         self.embed()
         qn = evaluate.l2_normalize_device(self.q_emb)
@@ -233,7 +240,36 @@ class Workload:
         cmc, mAP = evaluate.aggregate_cmc_map(rows[:, 0].astype(np.int64), rows[:, 1].astype(np.int64), rows[:, 2],
                                               rows[:, 3].astype(np.int64), self.G, 50)
         t2 = time.perf_counter()
+        self.rows = rows
         return cmc, mAP, ta - t0, t1 - ta, t2 - t1
+
+
+DUMP_EMB_ROWS = 4096  # --dump-outputs: sampled rows of the embeddings (x 1280 fp32 = 21 MB)
+DUMP_DIST_ROWS = 256  # ... and of the distance matrix (x 15913 fp32 = 16 MB)
+
+
+def dump_outputs(wl, cmc, mAP, out_dir):
+    """--dump-outputs: what the last timed step returned and left in the workload's buffers, as
+    out_dir/<name>.npy (float32 / float64, about 37 MB at Market size on one GPU):
+      cmc [50] f32, mAP [1] f64        the step's result (all ranks' queries)
+      eval_rows [Q, 4] f64             per query: valid, first match rank, AP, gallery kept
+      embeddings [<= 4096, 1280] f32   rows of this rank's (query then gallery) embeddings
+      distmat [<= 256, G] f32          rows of this rank's query x gallery distance matrix
+    The embedding and distance rows are a fixed sample (sorted, without replacement, seed 0)
+    when there are more than that; the inputs are seeded too, so the same arguments give the
+    same files from run to run.  Written by rank 0."""
+    os.makedirs(out_dir, exist_ok=True)
+
+    def sample(t, k):
+        n = t.shape[0]
+        idx = np.arange(n) if n <= k else np.sort(np.random.default_rng(0).choice(n, k, replace=False))
+        return t[torch.from_numpy(idx).to(t.device)].float().cpu().numpy()
+
+    arrays = {"cmc": np.asarray(cmc, np.float32), "mAP": np.asarray([mAP], np.float64),
+              "eval_rows": np.asarray(wl.rows, np.float64),
+              "embeddings": sample(wl.emb, DUMP_EMB_ROWS), "distmat": sample(wl.dist, DUMP_DIST_ROWS)}
+    for name, arr in arrays.items():
+        np.save(os.path.join(out_dir, name + ".npy"), np.ascontiguousarray(arr))
 
 
 MSMT17_RESID_GAIN = 4.0  # synthetic.vit_state_dict resid_gain of the MSMT17 leg's network
@@ -837,6 +873,11 @@ def _parse(argv=None):
     # nccl = RCCL over xGMI, one GPU per rank; gloo = host collectives, ranks may share a GPU
     # (LOCAL_RANK modulo the visible devices): the multi-rank test on a one-GPU box
     ap.add_argument("--backend", choices=("nccl", "gloo"), default="nccl")
+    # after the timed steps: the last step's arrays as DIR/<name>.npy (dump_outputs)
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None)
+    # the legs beside the headline (MSMT17, rooflines of the retrieval kernels, preprocess, JPEG,
+    # files -> mAP, re-rank, text, CPU baselines); a plain run does the Market steps only
+    ap.add_argument("--full", action="store_true")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-rerank", action="store_true")
     ap.add_argument("--no-msmt17", action="store_true")
@@ -899,7 +940,9 @@ def main():
     L.reidmi_prof_enable(0)
     elapsed = _max_over_ranks([elapsed], dev)[0]
     per_rank = _all_ranks([embed_s / a.steps, gather_s / a.steps, eval_s / a.steps], dev)
-    ms17 = None if a.no_msmt17 else msmt17_leg(None, dev, rank, world, a.batch)
+    if a.dump_outputs and rank == 0:
+        dump_outputs(wl, cmc, mAP, a.dump_outputs)
+    ms17 = msmt17_leg(None, dev, rank, world, a.batch) if a.full and not a.no_msmt17 else None
     if rank == 0:
         imgs = (wl.Q + wl.G) * a.steps
         avg_ms = ms.value / max(cnt.value, 1)
@@ -946,21 +989,21 @@ def main():
                                                             / 1e9, 2)}
         if ms17 is not None:
             line["msmt17"] = ms17
-        if not a.no_backend:
+        if a.full and not a.no_backend:
             line["backend"] = backend_rooflines(wl)
-        if not a.no_preprocess:
+        if a.full and not a.no_preprocess:
             line["preprocess"] = preprocess_leg(dev)
         # host-side baselines at N = 1 only (the other ranks would idle at the final barrier)
-        cpu = not a.no_cpu_baseline and world == 1
-        if not a.no_jpeg:
+        cpu = a.full and not a.no_cpu_baseline and world == 1
+        if a.full and not a.no_jpeg:
             line["jpeg"] = jpeg_leg(dev, cpu=cpu)
-        if not a.no_files and world == 1:
+        if a.full and not a.no_files and world == 1:
             line["files_to_map"] = files_leg(wl, dev, batch=a.files_batch)
             line["files_to_map"]["hbm_resident_step_s"] = round(elapsed / a.steps, 4)
         threads = min(os.cpu_count() or 1, int(os.environ.get("OMP_NUM_THREADS", "16") or 16))
-        if not a.no_rerank:
+        if a.full and not a.no_rerank:
             line["rerank"] = rerank_leg(dev, cpu=cpu, threads=threads)
-        if not a.no_text:
+        if a.full and not a.no_text:
             line["text"] = text_leg(dev, cpu=cpu, threads=threads)
         if cpu:
             line["cpu_baseline"] = cpu_baseline(wl, threads)

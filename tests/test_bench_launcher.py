@@ -47,6 +47,37 @@ def test_rank_envs():
 def test_parse_defaults_single_gpu():
     a = bench._parse([])
     assert a.gpus == 1 and a.backend == "nccl" and a.batch == 20480
+    assert a.full is False and a.dump_outputs is None  # a plain run: the Market steps alone
+
+
+def test_dump_outputs_files_and_fixed_sample(tmp_path):
+    """--dump-outputs: float32 / float64 .npy files, large arrays as the same sorted sample of
+    rows on every call, small ones whole."""
+    import types
+
+    import numpy as np
+    import torch
+    g = torch.Generator().manual_seed(3)
+    n_emb, n_q = bench.DUMP_EMB_ROWS + 77, bench.DUMP_DIST_ROWS - 5
+    wl = types.SimpleNamespace(emb=torch.randn(n_emb, 8, generator=g), dist=torch.randn(n_q, 33, generator=g),
+                               rows=np.arange(n_q * 4, dtype=np.float64).reshape(n_q, 4))
+    cmc = np.linspace(0.5, 1.0, 50).astype(np.float32)
+    outs = []
+    for d in ("a", "b"):
+        bench.dump_outputs(wl, cmc, np.float64(0.25), str(tmp_path / d))
+        assert sorted(os.listdir(tmp_path / d)) == ["cmc.npy", "distmat.npy", "embeddings.npy", "eval_rows.npy",
+                                                    "mAP.npy"]
+        outs.append({f[:-4]: np.load(tmp_path / d / f, allow_pickle=False) for f in os.listdir(tmp_path / d)})
+    a, b = outs
+    assert all(a[k].dtype in (np.float32, np.float64) and np.array_equal(a[k], b[k]) for k in a)
+    assert np.array_equal(a["cmc"], cmc) and a["mAP"].tolist() == [0.25] and np.array_equal(a["eval_rows"], wl.rows)
+    assert np.array_equal(a["distmat"], wl.dist.numpy())  # fewer rows than the cap: whole
+    emb = wl.emb.numpy()
+    assert a["embeddings"].shape == (bench.DUMP_EMB_ROWS, 8)
+    # the sampled rows are rows of the array, in ascending row order
+    idx = [int(np.flatnonzero((emb == r).all(1))[0]) for r in a["embeddings"][:64]]
+    assert idx == sorted(set(idx))
+    assert sum(v.nbytes for v in a.values()) <= 64 << 20
 
 
 def _child(tmp_path):

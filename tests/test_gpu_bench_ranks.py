@@ -14,8 +14,7 @@ import pytest
 pytestmark = pytest.mark.gpu
 
 REPO = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-QUICK = ["--steps", "1", "--warmup", "0", "--no-cpu-baseline", "--no-rerank", "--no-msmt17", "--no-text",
-         "--no-jpeg", "--no-backend", "--no-preprocess", "--no-files"]
+QUICK = ["--steps", "1", "--warmup", "0"]  # a plain run: no leg beside the Market step (those need --full)
 
 
 def _bench(*args):
@@ -28,10 +27,21 @@ def _bench(*args):
     return json.loads(lines[0])
 
 
-def test_bench_two_ranks_self_launched_equal_one(gpu):
-    one = _bench("--gpus", "1")
+def test_bench_two_ranks_self_launched_equal_one(gpu, tmp_path):
+    import numpy as np
+    one = _bench("--gpus", "1", "--dump-outputs", str(tmp_path))
     two = _bench("--gpus", "2", "--backend", "gloo")
     assert one["n_gpus"] == 1 and two["n_gpus"] == 2
+    # a plain run carries the headline and none of the --full legs
+    assert one["steps"] == 1 and one["ms_per_step"] > 0 and one["unit"] == "imgs/s"
+    assert not {"msmt17", "backend", "preprocess", "jpeg", "files_to_map", "rerank", "text", "cpu_baseline"} & set(one)
+    # --dump-outputs: what the timed step returned, as the line reports it
+    out = {f[:-4]: np.load(tmp_path / f, allow_pickle=False) for f in os.listdir(tmp_path)}
+    assert sorted(out) == ["cmc", "distmat", "embeddings", "eval_rows", "mAP"]
+    assert round(float(out["mAP"][0]), 6) == one["mAP"] and round(float(out["cmc"][0]), 6) == one["rank1"]
+    assert out["eval_rows"].shape == (3368, 4) and out["distmat"].shape == (256, 15913)
+    assert out["embeddings"].shape == (4096, 1280) and np.isfinite(out["embeddings"]).all()
+    assert sum(v.nbytes for v in out.values()) <= 64 << 20
     assert two["config"]["parallelism"].startswith("dp2")
     assert two["mAP"] == one["mAP"] and two["rank1"] == one["rank1"]
     rk = two["ranks"]

@@ -9,6 +9,8 @@ set -e
 cd /tmp && export TMPDIR=/tmp && cd "$GRAFT_REPO_ROOT"
 mkdir -p gpurun_out
 M=$(( ${BATCH:-19281} * 211 ))
+# the kernel stats cover every leg of the benchmark, not the Market steps alone
+BENCH_ARGS=${BENCH_ARGS:---full}
 timeout -k 10 400 rocprofv3 --kernel-trace --stats --output-format csv -d gpurun_out/prof_bench -o bench -- \
   python bench.py ${BENCH_ARGS} > gpurun_out/bench_under_rocprof.json
 for c in FETCH_SIZE WRITE_SIZE; do
