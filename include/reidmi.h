@@ -131,7 +131,7 @@ int reidmi_rr_feat16(const float* feat, int64_t N, int64_t D, int64_t ldf, void*
  * nmax2 of reidmi_rr_rank_rows_f16. */
 int reidmi_rr_norm_max(const float* sqn, const float* nrm, int64_t N, float* out2, void* stream);
 /* reidmi_rr_rank_rows with an fp16 MFMA pre-filter (same rank_out / rowmax_out bits): the fp16
- * product bounds every exact distance (error bound in backend.hip rank_select_kernel); only the
+ * product bounds every exact distance (error bound in backend.hip, above rank_select1_kernel); only the
  * candidates are recomputed with the exact fp32 chain.  Default form (sample stride 16, for N
  * >= 4096): per-row thresholds from every 16th item, then the selection runs inside the GEMM's
  * epilogue (survivor lists, no N-wide row in HBM; when one call covers all N rows and the lists

@@ -27,18 +27,6 @@ int reidmi_gemm_f16_tiled(int epi, const void* A, int64_t lda, const void* W, in
                           int64_t K, const float* bias, const void* rowstat, const float* colsum, void* out,
                           int64_t ldc, int tile, int ngroups, void* stream);
 
-/* ln_1 -> in_proj -> SDPA of one encoder block (custom_clip_model.py:22-27) with ln_1 folded
- * (reidmi_gemm_f16's rowstat / colsum / folded bias; wq [3W][ldw] = the folded in_proj weight):
- * o [nseq*L][W] fp16 = attention output, token-major.  fused = 1: one kernel, q / k / v stay on
- * chip (192 < L <= 224, non-causal; q, k, vt may be NULL); fused = 0: the QKV GEMM into q, k
- * [nseq*H][L][64] and vt [nseq*H][64][reidmi_attn_lpad(L)] then reidmi_mhsa_f16 — what
- * reidmi_vit_forward runs (the fused kernel is bit-identical but measured slower). */
-int reidmi_qkv_attention_f16(const void* x, int64_t ldx, const void* wq, int64_t ldw, const float* bias,
-                             const float* colsum, const void* rowstat, int64_t nseq, int L, int H, int W, void* q,
-                             void* k, void* vt, void* o, int fused, void* stream);
-
-/* The QKV GEMM alone (ln_1 fold + the head split reidmi_vit_forward uses): x [nseq*L][lda],
- * W [3*H*64][ldw] -> q, k [nseq*H][L][64], vt [nseq*H][64][lpad] (lpad = reidmi_attn_lpad(L)). */
 /* One-wave-per-SIMD GEMM prototype (gemm.hip gemm_w4_kernel): out fp16 = A.W^T + bias, same MFMA
  * chain as reidmi_gemm_f16 epi 0 (bit-identical); nostore: the values are computed, not stored.
  * N % 256 == 0, K % 64 == 0, K >= 128. */
@@ -52,6 +40,8 @@ int reidmi_gemm_f16_w4(const void* A, int64_t lda, const void* W, int64_t ldw, i
 int reidmi_mhsa_f16_rr(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H,
                        void* stream);
 
+/* The QKV GEMM alone (ln_1 fold + the head split reidmi_vit_forward uses): x [nseq*L][lda],
+ * W [3*H*64][ldw] -> q, k [nseq*H][L][64], vt [nseq*H][64][lpad] (lpad = reidmi_attn_lpad(L)). */
 int reidmi_gemm_f16_qkv(const void* A, int64_t lda, const void* W, int64_t ldw, int64_t nseq, int L, int H,
                         const float* bias, const void* rowstat, const float* colsum, void* q, void* k, void* vt,
                         int lpad, void* stream);

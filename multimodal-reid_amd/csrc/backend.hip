@@ -159,26 +159,19 @@ __global__ __launch_bounds__(256) void distmat_f32_kernel(
 // result is bit-identical to distmat_f32_kernel (and to the oracle's fmaf chain).
 // K-step 16 (33 KB of LDS, 112 VGPRs): four workgroups per CU; K-step 32 ran two (66 KB) and
 // was 5 % slower at MSMT17 / re-rank-chunk sizes (profiles/r02/distmat_kstep_ab.txt).  The
-// macros are A/B hooks for tools/build_variant.py.
+// macro is an A/B hook for tools/build_variant.py.
 #ifndef DM2_BK_
 #define DM2_BK_ 16
 #endif
-#ifndef DM2_MINWG_
-#define DM2_MINWG_ 4
+#if !defined(REIDMI_TOOLS) && (DM2_BK_ != 16 || defined(RS_STATS))
+#error "backend.hip: DM2_BK_ / RS_STATS variants build only with -DREIDMI_TOOLS (never into libreidmi.so)"
 #endif
-#ifndef DM2_BAND
-#define DM2_BAND 4
-#endif
-#if !defined(REIDMI_TOOLS) && (DM2_BK_ != 16 || DM2_MINWG_ != 4 || DM2_BAND != 4 || defined(RS_STATS) || \
-                               defined(RS_SINGLE_PASS) || defined(EV_STAMPS) || defined(EV_PREFETCH) || defined(EV_U1))
-#error "backend.hip: DM2_* / RS_* / EV_* variants build only with -DREIDMI_TOOLS (never into libreidmi.so)"
-#endif
-constexpr int DM2_BK = DM2_BK_, DM2_LD = DM_BM + 1;
+constexpr int DM2_BK = DM2_BK_, DM2_MINWG = 4, DM2_BAND = 4, DM2_LD = DM_BM + 1;
 constexpr int DM2_F4 = DM2_BK / 4;            // float4 per operand row and K-step
 constexpr int DM2_U = DM_BM * DM2_F4 / 256;   // float4 staging slots per thread and operand
 
 template <bool COSINE, bool SYM = false>
-__global__ __launch_bounds__(256, DM2_MINWG_) void distmat2_f32_kernel(
+__global__ __launch_bounds__(256, DM2_MINWG) void distmat2_f32_kernel(
     const float* __restrict__ q, const float* __restrict__ g, const float* __restrict__ qq,
     const float* __restrict__ gg, int64_t Q, int64_t G, int64_t D, int64_t ldq, int64_t ldg,
     float* __restrict__ out, int64_t ldo) {
@@ -479,7 +472,6 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
 // candidate lists overflow, or with a non-finite bound or
 // max, is marked in need[] for the exact rows (reranking.HipStages.rank_rows runs them through
 // the exact distance kernel + selection).
-constexpr int RS_CCAP = 2048, RS_MCAP = 512;
 #ifndef DE_UNROLL
 #define DE_UNROLL 16
 #endif
@@ -526,94 +518,6 @@ __device__ __forceinline__ float rr_width(float s_i, float n_i, float n_max, flo
     return 2.0f * e * (1.0f + 0x1p-10f) + 0x1p-20f * (s_i + s_max + e);
 }
 
-// Rows of the k-reciprocal R2 from the pre-filter bounds hi ([rows][ldd] fp32, the EPI_RRHI
-// GEMM epilogue: gemm.h rr_hi), lo = hi - w_i (rr_width): the K-th smallest hi bounds the K-th
-// smallest exact distance, every item with lo <= that bound is a candidate of the top K, every
-// item with hi >= the largest lo a candidate of the row max; both are recomputed exactly.
-__global__ __launch_bounds__(256) void rank_select_kernel(const float* __restrict__ dot, int64_t ldd,
-                                                          const float* __restrict__ feat, int64_t ldf, int D,
-                                                          const float* __restrict__ sqn, const float* __restrict__ nrm,
-                                                          int64_t row0, int64_t N, int K, float c_rel, float c_abs,
-                                                          float c_d, const float* __restrict__ nmax2,
-                                                          int32_t* __restrict__ rank_out,
-                                                          float* __restrict__ rowmax_out, int32_t* __restrict__ need) {
-    __shared__ TkLds L;
-    __shared__ float cv[RS_CCAP];
-    __shared__ int ci[RS_CCAP];
-    __shared__ int mi[RS_MCAP];
-    __shared__ int s_nc, s_nm, s_bad;
-    __shared__ float red[4];
-    const int64_t r = blockIdx.x, i = row0 + r;
-    const float* drow = dot + r * ldd;
-    const float w = rr_width(sqn[i], nrm[i], nmax2[0], nmax2[1], c_rel, c_abs, c_d);
-    auto bounds = [&](int64_t j, float& lo, float& hi) {
-        hi = drow[j];
-        lo = hi - w;
-    };
-    if (threadIdx.x == 0) { s_nc = 0; s_nm = 0; s_bad = 0; }
-    // pass A: tau = the K-th smallest upper bound; the largest lower bound
-    topk_row_dev(
-        [&](int64_t j) {
-            float lo, hi;
-            bounds(j, lo, hi);
-            return hi;
-        },
-        N, K, L);
-    const float tau = L.sv[K - 1];
-    float ml = -__builtin_inff();
-    bool bad = !(tau <= 3.0e38f && tau >= -3.0e38f);
-    for (int64_t j = threadIdx.x; j < N; j += blockDim.x) {
-        float lo, hi;
-        bounds(j, lo, hi);
-        ml = fmaxf(ml, lo);
-        bad = bad || !(lo == lo && hi == hi && hi < __builtin_inff());
-    }
-    if (bad) s_bad = 1;
-    const float mlo = block_max(ml, red);
-    const float thr = tau + fabsf(tau) * 0x1p-21f + 1e-37f;
-    // pass B: candidate lists
-    if (!s_bad) {
-        for (int64_t j = threadIdx.x; j < N; j += blockDim.x) {
-            float lo, hi;
-            bounds(j, lo, hi);
-            if (lo <= thr) {
-                const int p = atomicAdd(&s_nc, 1);
-                if (p < RS_CCAP) ci[p] = (int)j;
-            }
-            if (hi >= mlo) {
-                const int p = atomicAdd(&s_nm, 1);
-                if (p < RS_MCAP) mi[p] = (int)j;
-            }
-        }
-    }
-    __syncthreads();
-    const int nc = s_nc, nm = s_nm;
-    bool exact = s_bad || nc > RS_CCAP || nm > RS_MCAP;
-    float rmax = 0.0f;
-    if (!exact) {
-        float m = -__builtin_inff();
-        for (int t = threadIdx.x; t < nm; t += blockDim.x) m = fmaxf(m, dist_exact(feat, ldf, D, sqn, i, mi[t]));
-        rmax = block_max(m, red);
-        exact = !(rmax > 0.0f && rmax < __builtin_inff());  // degenerate rows: the exact path
-    }
-    if (!exact) {
-        for (int t = threadIdx.x; t < nc; t += blockDim.x) cv[t] = dist_exact(feat, ldf, D, sqn, i, ci[t]) / rmax;
-        const int P = pow2_ceil(nc < 2 ? 2 : nc);
-        for (int t = nc + threadIdx.x; t < P; t += blockDim.x) { cv[t] = __builtin_inff(); ci[t] = 0x7fffffff; }
-        __syncthreads();
-        bitonic_sort_kv(cv, ci, P);
-        for (int t = threadIdx.x; t < K; t += blockDim.x) rank_out[r * K + t] = ci[t];
-        if (threadIdx.x == 0) {
-            rowmax_out[r] = rmax;
-            need[r] = 0;
-        }
-        return;
-    }
-    // the row needs the exact path (its distances are too concentrated for the bound, or not
-    // finite): the caller runs reidmi_rr_rank_rows' exact MFMA rows for the rows marked here
-    if (threadIdx.x == 0) need[r] = 1;
-}
-
 // Keep the entries j of idx[0, n) with keep(j) (order preserved, in place); one full wave.
 template <typename KEEP>
 __device__ int compact_wave(int* idx, int n, KEEP keep) {
@@ -630,11 +534,16 @@ __device__ int compact_wave(int* idx, int n, KEEP keep) {
     return w;
 }
 
-// Single-pass form of rank_select_kernel (same bound, same output bits): one stream over the
-// row feeds the K-smallest-hi selection and both candidate lists at once, against the running
-// thresholds -- the running K-th smallest hi only decreases and the running max lo only
-// increases, so each list holds a superset of the final one; a list near capacity, and both
-// lists at the end, are filtered against the current thresholds (exact set of the 3-pass form).
+// Rows of the k-reciprocal R2 from the pre-filter bounds hi ([rows][ldd] fp32, the EPI_RRHI
+// GEMM epilogue: gemm.h rr_hi), lo = hi - w_i (rr_width): the K-th smallest hi bounds the K-th
+// smallest exact distance, every item with lo <= that bound is a candidate of the top K, every
+// item with hi >= the largest lo a candidate of the row max; both are recomputed exactly.
+// One stream over the row feeds the K-smallest-hi selection and both candidate lists at once,
+// against the running thresholds -- the running K-th smallest hi only decreases and the
+// running max lo only increases, so each list holds a superset of the final one; a list near
+// capacity, and both lists at the end, are filtered against the current thresholds (the exact
+// set that three separate passes over the row give; that earlier kernel ran 0.116 s against
+// 0.055 s on MSMT17's R2, DESIGN.md §4, and was removed with its RS_SINGLE_PASS switch).
 #ifndef RS1_CHUNK
 #define RS1_CHUNK 1024
 #endif
@@ -1351,14 +1260,8 @@ __global__ void ev_pack_kernel(const int64_t* __restrict__ gp, int64_t G, int64_
 // table of the positives (no per-item binary search: that search was 2/3 of the kernel).
 // Wave 0 scans the histogram into ranks and sums the AP lane-parallel.  Queries with more
 // than EVW_MAXP positives or EVW_MAXJ junk items are left to eval_rows_kernel (valid = 2).
-// Per-phase cycle stamps: profiles/r02/eval_rows_phase_stamps.txt (-DEV_STAMPS build).
+// Per-phase cycle stamps: profiles/r02/eval_rows_phase_stamps.txt.
 constexpr int EVW_MAXP = 512, EVW_MAXJ = 256, EVW_T = 1024;
-#ifndef EV_PREFETCH
-#define EV_PREFETCH 0
-#endif
-#ifndef EV_U1  // 16-byte label loads in flight per thread in the label pass
-#define EV_U1 8
-#endif
 
 __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void eval_rows_wg_kernel(
     const float* __restrict__ dist, int64_t G, int64_t ld, const int64_t* __restrict__ qp,
@@ -1378,18 +1281,13 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void e
     __shared__ int2 bucket[EVW_T + 1];
     __shared__ int trash[256];  // one histogram slot per thread for the items not binned
     const int tid = threadIdx.x, lane = tid & 63;
-#ifdef EV_STAMPS
-    const uint64_t t0 = __builtin_amdgcn_s_memtime(), rt0 = __builtin_amdgcn_s_memrealtime();
-    uint64_t t1 = 0, t2 = 0, t3 = 0;
-#endif
     const int64_t q = blockIdx.x;
     const float* row = dist + q * ld;
     const int64_t qpid = qp[q], qcam = qc[q];
     const uint64_t below = (1ull << lane) - 1;
     int* sidx = (int*)bucket;  // same-pid gallery indices of pass 1 (the bucket table comes later)
     constexpr int SCAP = EVW_MAXP + EVW_MAXJ;
-    // the distance pass's layout (16-byte loads after a scalar head) and its first chunk,
-    // loaded now so its latency hides behind the label pass and the sort
+    // the distance pass's layout (16-byte loads after a scalar head)
     const int head = (int)(((16 - ((uintptr_t)row & 15)) & 15) >> 2);  // scalar items before 16-B alignment
     const int h = head < G ? head : (int)G;
     const int nv = (int)((G - h) >> 2);  // float4 groups (G < 2^31)
@@ -1403,9 +1301,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void e
             v[u] = r4[g < nv ? g : nv - 1];
         }
     };
-#if EV_PREFETCH
-    if (nv > 0) load_chunk(0);
-#endif
     if (tid == 0) { s_m = 0; s_nj = 0; s_ns = 0; }
     __syncthreads();
     // ---- pass 1: labels -> indices of the gallery items with the query's pid (ballot
@@ -1423,7 +1318,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void e
     if ((uint64_t)(phi - plo) < 0xFFFFull) {  // packed uint16 labels, 8 per 16-byte load
         if (qpid >= plo && qpid <= phi) {
             const uint16_t key = (uint16_t)(qpid - plo);
-            constexpr int U1 = EV_U1, CH = 2048 * U1;
+            constexpr int U1 = 8, CH = 2048 * U1;  // U1: 16-byte label loads in flight per thread
             const int64_t nch = (G + CH - 1) / CH;
             const int64_t c0 = (q * 37) % nch;
             const int64_t n8 = (G + 7) / 8;
@@ -1494,9 +1389,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void e
     }
     __syncthreads();
     const int m = s_m, nj = s_nj;
-#ifdef EV_STAMPS
-    t1 = __builtin_amdgcn_s_memtime();
-#endif
     if (ns > SCAP || m > EVW_MAXP || nj > EVW_MAXJ) {  // eval_rows_kernel (large lists) takes it
         if (tid == 0) {
             valid[q] = 2;
@@ -1561,9 +1453,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void e
         bucket[t] = make_int2(n > 0 ? __float_as_int(pv[lo]) : 0x7f800000, lo | (n > 1 ? MULTI : 0));
     }
     __syncthreads();
-#ifdef EV_STAMPS
-    t2 = __builtin_amdgcn_s_memtime();
-#endif
     // b for an item of bucket t with entry e: the exact (value, index) walk over the bucket
     auto walk = [&](int t, int2 e, float v, int j) {
         int b = e.y & 0xFFFF;
@@ -1581,7 +1470,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void e
     if (tid < h) bin(row[tid], tid);
     int* const mytrash = &trash[tid];
     for (int g0 = 0; g0 < nv; g0 += 256 * U2) {
-        if (!EV_PREFETCH || g0 > 0) load_chunk(g0);
+        load_chunk(g0);
 #pragma unroll
         for (int u = 0; u < U2; u++) {
             const int g = g0 + u * 256 + tid;
@@ -1620,9 +1509,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void e
     }
     for (int64_t j = h + (int64_t)nv * 4 + tid; j < G; j += 256) bin(row[j], (int)j);
     __syncthreads();
-#ifdef EV_STAMPS
-    t3 = __builtin_amdgcn_s_memtime();
-#endif
     // ---- ranks (wave 0): inclusive scan of hist, minus the item itself and the junk before it
     if (tid < 64) {
         int carry = 0;
@@ -1656,12 +1542,6 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(8))) void e
             valid[q] = 1;
             first[q] = rk[0];
             ap[q] = sum / (double)m;
-#ifdef EV_STAMPS
-            const uint64_t t4 = __builtin_amdgcn_s_memtime();
-            first[q] = (int64_t)((t1 - t0) | ((t2 - t1) << 32));
-            nkept[q] = (int64_t)((t3 - t2) | ((t4 - t3) << 32));
-            ap[q] = (double)rt0;
-#endif
         }
     }
 }
@@ -1809,7 +1689,7 @@ __global__ __launch_bounds__(256) void eval_rows_kernel(
 }
 
 // The pair bound's constants for D-dimensional features (fp16-rounded operands, fp32 MFMA
-// accumulation; the derivation is in rank_select_kernel's description of the bound).
+// accumulation; the derivation is in the description of the bound above rank_select1_kernel).
 void rank_select_consts(int D, float c[3]) {
     const double c_rel = 2.0 * (0x1p-10 + 0x1p-22 + 2.02 * D * 0x1p-24) + 2.02 * 0x1p-23;
     const double c_abs = 2.01 * 0x1p-25 * std::sqrt((double)D);
@@ -1853,7 +1733,7 @@ int norm_max_launch(const float* sqn, const float* nrm, int64_t N, float* out2, 
     return OK;
 }
 
-// rank_select_kernel over rows [row0, row0 + rows) of the pre-filter bounds `dot` ([rows][ldd]
+// rank_select1_kernel over rows [row0, row0 + rows) of the pre-filter bounds `dot` ([rows][ldd]
 // fp32 hi, ldd >= N, the EPI_RRHI GEMM), nmax2 = norm_max_kernel's maxima.
 int rank_select_launch(float* dot, int64_t ldd, const float* feat, int64_t ldf, int D, const float* sqn,
                        const float* nrm, const float* nmax2, int64_t row0, int64_t rows, int64_t N, int K,
@@ -1864,12 +1744,8 @@ int rank_select_launch(float* dot, int64_t ldd, const float* feat, int64_t ldf, 
     if (rows == 0) return OK;
     float c[3];
     rank_select_consts(D, c);
-#ifndef RS_SINGLE_PASS
-#define RS_SINGLE_PASS 1
-#endif
-    hipLaunchKernelGGL(RS_SINGLE_PASS ? rank_select1_kernel : rank_select_kernel, dim3((unsigned)rows), dim3(256), 0,
-                       s, dot, ldd, feat, ldf, D, sqn, nrm, row0, N, K, c[0], c[1], c[2], nmax2, rank_out, rowmax_out,
-                       need);
+    hipLaunchKernelGGL(rank_select1_kernel, dim3((unsigned)rows), dim3(256), 0, s, dot, ldd, feat, ldf, D, sqn, nrm,
+                       row0, N, K, c[0], c[1], c[2], nmax2, rank_out, rowmax_out, need);
     RM_LAUNCHED();
     return OK;
 }

@@ -21,15 +21,6 @@ namespace reidmi {
 int mhsa(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H, bool causal,
          hipStream_t s);
 int attn_lpad(int L);
-#ifdef REIDMI_TOOLS
-// The fused QKV + attention kernel is bit-identical to the two-kernel block but measured slower
-// at the bench batch (B = 1024, L = 211: 1.20 ms vs 1.09-1.12 ms for QKV GEMM + mhsa,
-// tools/qkv_attn_ab.py, profiles/r03), so vision blocks run the two kernels and the kernel is
-// built into the tools library only.
-bool qkv_attn_fits(int L, int W, bool causal);
-int qkv_attn(const void* x, int64_t ldx, const void* wq, int64_t ldw, const float* bias, const float* colsum,
-             const void* rowstat, int64_t nseq, int L, int H, int W, void* o, hipStream_t s);
-#endif
 int mhsa_cls(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H, hipStream_t s);
 int64_t cls_attn_nokv_ws_bytes(int64_t nseq, int W);
 int cls_attn_nokv(const void* x, const void* rs, const void* q, const void* wqkv, const float* colsum,
@@ -770,34 +761,3 @@ REIDMI_API int reidmi_gemm_f16_resid_partials(const void* A, int64_t lda, const 
     return gemm_f16(EPI_RESID_F16, (const _Float16*)A, lda, (const _Float16*)Wt, ldw, M, (int)N, (int)K, e,
                     (hipStream_t)stream);
 }
-
-#ifdef REIDMI_TOOLS
-// ln_1-folded QKV projection + attention of one block (custom_clip_model.py:22-27) on its own,
-// for tests / A-B timing (tools library, include/reidmi_tools.h): fused = 1 the single fused kernel, 0 the QKV GEMM (head-split
-// epilogue into q, k [nseq*H][L][64], vt [nseq*H][64][reidmi_attn_lpad(L)]) then the attention
-// kernel.  The two are bit-identical (same MFMA chains, same roundings).
-REIDMI_API int reidmi_qkv_attention_f16(const void* x, int64_t ldx, const void* wq, int64_t ldw, const float* bias,
-                                        const float* colsum, const void* rowstat, int64_t nseq, int L, int H, int W,
-                                        void* q, void* k, void* vt, void* o, int fused, void* stream) {
-    hipStream_t s = (hipStream_t)stream;
-    RM_REQUIRE(W == H * 64 && L > 0 && nseq >= 0 && rowstat && colsum && bias, "qkv_attention: bad arguments");
-    if (fused) {
-        RM_REQUIRE(qkv_attn_fits(L, W, false), "qkv_attention: the fused kernel takes 192 < L <= 224 tokens");
-        return qkv_attn(x, ldx, wq, ldw, bias, colsum, rowstat, nseq, L, H, W, o, s);
-    }
-    RM_REQUIRE(q && k && vt, "qkv_attention: q / k / vt scratch required for the unfused path");
-    EpiArgs ea{};
-    ea.bias = bias;
-    ea.rowstat = (const float2*)rowstat;
-    ea.colsum = colsum;
-    ea.q = q;
-    ea.k = k;
-    ea.vt = vt;
-    ea.seq = L;
-    ea.heads = H;
-    ea.lpad = attn_lpad(L);
-    int rc;
-    if ((rc = gemm_f16(EPI_QKV, x, ldx, wq, ldw, nseq * L, 3 * W, W, ea, s))) return rc;
-    return mhsa(q, k, vt, o, nseq, L, H, false, s);
-}
-#endif  // REIDMI_TOOLS

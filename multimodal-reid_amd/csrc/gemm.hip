@@ -43,9 +43,6 @@ constexpr int GB_M = 128, GB_N = 128, GB_K = 64;
 #ifndef GEMM_VAR_NOSTORE
 #define GEMM_VAR_NOSTORE 0
 #endif
-#ifndef GEMM_VAR_GELU1  // timing-only (wrong results): QuickGELU with one transcendental per element
-#define GEMM_VAR_GELU1 0   // (VERDICT r5 lever (b): the ceiling of any single-transcendental form)
-#endif
 #ifndef GEMM_VAR_NOGELU
 #define GEMM_VAR_NOGELU 0
 #endif
@@ -54,27 +51,6 @@ constexpr int GB_M = 128, GB_N = 128, GB_K = 64;
 #endif
 #ifndef GEMM_VAR_NORESLOAD
 #define GEMM_VAR_NORESLOAD 0
-#endif
-#ifndef GEMM_VAR_STAGGER  // s_sleep(GEMM_VAR_STAG_SLP) rounds before a workgroup starts:
-#define GEMM_VAR_STAGGER 0  // STAGGER x ((bid >> GEMM_VAR_STAG_SHIFT) & GEMM_VAR_STAG_MASK)
-#endif
-#ifndef GEMM_VAR_STAG_SHIFT
-#define GEMM_VAR_STAG_SHIFT 0
-#endif
-#ifndef GEMM_VAR_STAG_MASK
-#define GEMM_VAR_STAG_MASK 1
-#endif
-#ifndef GEMM_VAR_STAG_SLP  // 64 x SLP cycles per round (127: ~8k cycles, ~4 us)
-#define GEMM_VAR_STAG_SLP 127
-#endif
-#ifndef GEMM_VAR_DIAG_LOAD0  // timing-only (wrong results): LOAD 0 reads no W fragments (4 of its 12 reads)
-#define GEMM_VAR_DIAG_LOAD0 0
-#endif
-#ifndef GEMM_VAR_RPRE  // persistent tile: residual rows loaded before the bias / fold arithmetic
-#define GEMM_VAR_RPRE 1
-#endif
-#ifndef GEMM_VAR_FB2  // persistent tile: keep both column halves' W fragments (LOAD 3 reads none)
-#define GEMM_VAR_FB2 1
 #endif
 #ifndef GEMM_VAR_NODMA  // timing-only (wrong results): no operand DMA inside the K-loop
 #define GEMM_VAR_NODMA 0
@@ -88,11 +64,9 @@ constexpr int GB_M = 128, GB_N = 128, GB_K = 64;
 // The A/B hooks above compile other kernels (the timing-only ones give wrong results by design):
 // any value but the shipped one is refused outside a tools / variant build (-DREIDMI_TOOLS:
 // libreidmi_tools.so, tools/build_variant.py), so none can enter libreidmi.so.
-#if !defined(REIDMI_TOOLS) &&                                                                              \
-    (GEMM_VAR_NOSTORE != 0 || GEMM_VAR_NOGELU != 0 || GEMM_VAR_GELU1 != 0 || GEMM_VAR_NOPSTAT != 0 || GEMM_VAR_NORESLOAD != 0 ||   \
-     GEMM_VAR_STAGGER != 0 || GEMM_VAR_DIAG_LOAD0 != 0 || GEMM_VAR_RPRE != 1 || GEMM_VAR_FB2 != 1 ||       \
-     GEMM_VAR_STAG_SHIFT != 0 || GEMM_VAR_STAG_MASK != 1 || GEMM_VAR_STAG_SLP != 127 || GEMM_VAR_NODMA != 0 || \
-     GEMM_VAR_ASAME != 0 || GEMM_VAR_NOWAIT != 0)
+#if !defined(REIDMI_TOOLS) &&                                                                             \
+    (GEMM_VAR_NOSTORE != 0 || GEMM_VAR_NOGELU != 0 || GEMM_VAR_NOPSTAT != 0 || GEMM_VAR_NORESLOAD != 0 || \
+     GEMM_VAR_NODMA != 0 || GEMM_VAR_ASAME != 0 || GEMM_VAR_NOWAIT != 0)
 #error "gemm.hip: GEMM_VAR_* variants build only with -DREIDMI_TOOLS (never into libreidmi.so)"
 #endif
 
@@ -111,11 +85,7 @@ __device__ __forceinline__ uint32_t cvt_pk_f16(float a, float b) {
 __device__ __forceinline__ f32x2v quick_gelu2(f32x2v x) {
     const f32x2v y = x * -2.4554669595930157f;
     const f32x2v d = f32x2v{__builtin_amdgcn_exp2f(y.x), __builtin_amdgcn_exp2f(y.y)} + 1.0f;
-#if GEMM_VAR_GELU1
-    return x * (2.0f - d);  // one packed FMA in place of the two v_rcp_f32: any one-transcendental form costs more
-#else
     return x * f32x2v{__builtin_amdgcn_rcpf(d.x), __builtin_amdgcn_rcpf(d.y)};
-#endif
 }
 
 __device__ __forceinline__ f32x4 mfma16(const f16x8& w, const f16x8& a, const f32x4& c) {
@@ -898,10 +868,7 @@ __global__ __launch_bounds__(512, 2) void gemm_persistent_kernel(const _Float16*
     const int lo = (int)(sub * xs / xper), hi = (int)(sub * (xs + 1) / xper);
     const int first = lo + bid / ng;
     if (first >= hi) return;
-    if constexpr (GEMM_VAR_STAGGER > 0) {  // timing variant: workgroups start at different times (desynchronised epilogues)
-        const int rounds = GEMM_VAR_STAGGER * ((bid >> GEMM_VAR_STAG_SHIFT) & GEMM_VAR_STAG_MASK);
-        for (int i = 0; i < rounds; i++) __builtin_amdgcn_s_sleep(GEMM_VAR_STAG_SLP);
-    } else if constexpr (EPI == EPI_RESID_F16) {
+    if constexpr (EPI == EPI_RESID_F16) {
         // The residual epilogue reads and writes 2 x 128 KB per tile; with every workgroup in
         // step those bursts hit HBM together.  Odd workgroups start ~8k cycles (~1/8 of an
         // out_proj tile) late: out_proj -2.5 %, c_proj -1.7 %; no effect on the other epilogues
@@ -997,12 +964,11 @@ __global__ __launch_bounds__(512, 2) void gemm_persistent_kernel(const _Float16*
     } while (0)
 #define G5_LDS_DONE() asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory")
 
-    // FB2: both column halves' W fragments stay in registers (6 more VGPRs as allocated), so
+    // Both column halves' W fragments stay in registers (6 more VGPRs as allocated), so
     // LOAD 3 reads nothing: the K-step's W fragments are read from LDS once, not 1.5 times
     // (-14 % LDS read bytes; c_fc / QKV / c_proj +1 %, out_proj even,
     // profiles/r04/gemm_fb2_ab.txt)
-    constexpr bool FB2 = GEMM_VAR_FB2 != 0;
-    f16x8 fa[4][2], fbq[FB2 ? 2 : 1][2][2];
+    f16x8 fa[4][2], fbq[2][2][2];
     f32x4 acc[8][4];
     auto load_a = [&](const _Float16* sA, int qm) {
 #pragma unroll
@@ -1016,7 +982,7 @@ __global__ __launch_bounds__(512, 2) void gemm_persistent_kernel(const _Float16*
         for (int j = 0; j < 2; j++)
 #pragma unroll
             for (int ks = 0; ks < 2; ks++)
-                fbq[FB2 ? qn : 0][j][ks] =
+                fbq[qn][j][ks] =
                     *(const f16x8*)(sW + swz(wc * 64 + qn * 32 + j * 16 + (lane & 15), ks * 4 + (lane >> 4)));
     };
     // FIRST: the tile's first K-step starts every accumulator chain from an inline-constant 0
@@ -1029,7 +995,7 @@ __global__ __launch_bounds__(512, 2) void gemm_persistent_kernel(const _Float16*
 #pragma unroll
                 for (int j = 0; j < 2; j++) {
                     f32x4& c = acc[qm * 4 + i][qn * 2 + j];
-                    const f16x8& b = fbq[FB2 ? qn : 0][j][ks];
+                    const f16x8& b = fbq[qn][j][ks];
                     if constexpr (decltype(firstc)::value)
                         c = mfma16(b, fa[i][ks], ks == 0 ? f32x4{0.f, 0.f, 0.f, 0.f} : c);
                     else
@@ -1087,7 +1053,7 @@ __global__ __launch_bounds__(512, 2) void gemm_persistent_kernel(const _Float16*
             const _Float16* sW = sA + G2_M * GB_K;
             // LOAD 0 / COMPUTE (0,0)
             load_a(sA, 0);
-            if constexpr (!GEMM_VAR_DIAG_LOAD0) load_b(sW, 0);
+            load_b(sW, 0);
             if (kt == 0 && has_bias)
                 __builtin_amdgcn_global_load_lds(ea.bias + (nb0 + tnt) * G2_N + lane * 4, (lds_ptr_t)bias_slot,
                                                  16, 0, 0);
@@ -1131,8 +1097,7 @@ __global__ __launch_bounds__(512, 2) void gemm_persistent_kernel(const _Float16*
             G5_BARRIER();
             compute(1, 1, firstc);
             G5_BARRIER();
-            // LOAD 3 / COMPUTE (1,0)
-            if constexpr (!FB2) load_b(sW, 0);
+            // LOAD 3 (no LDS reads: W fragments of column half 0 are still in fbq[0]) / COMPUTE (1,0)
             if (has2) {
                 if constexpr (KDMA) issue_a(buf, 1, p2);
                 G5_LDS_DONE();
@@ -1183,7 +1148,7 @@ __global__ __launch_bounds__(512, 2) void gemm_persistent_kernel(const _Float16*
         // residual epilogue: its row reads go out before the bias arithmetic (after the next
         // tile's early DMA, so the deferred-store count EpiVm is unchanged), their latency
         // then runs beside it
-        constexpr bool RPRE = EPI == EPI_RESID_F16 && GEMM_VAR_RPRE && !GEMM_VAR_NORESLOAD;
+        constexpr bool RPRE = EPI == EPI_RESID_F16 && !GEMM_VAR_NORESLOAD;
         f16x8 xres[RPRE ? 8 : 1][2];
         if constexpr (RPRE) resid_rows_load<8>(ea, m0 + wr * 128, n0 + wc * 64, M, xres);
         if (has_bias) {

@@ -60,7 +60,7 @@ def test_tools_library_exports_variants_product_does_not():
     assert not missing, missing
 
 
-@pytest.mark.parametrize("src,define", [("gemm.hip", "-DGEMM_VAR_NOSTORE=1"), ("gemm.hip", "-DGEMM_VAR_FB2=0"),
+@pytest.mark.parametrize("src,define", [("gemm.hip", "-DGEMM_VAR_NOSTORE=1"), ("gemm.hip", "-DGEMM_VAR_NOWAIT=1"),
                                         ("gemm.hip", "-DGEMM_VAR_NODMA=1"),
                                         ("backend.hip", "-DDM2_BK_=32"), ("backend.hip", "-DRS_STATS")])
 def test_variant_macros_refused_outside_tools_builds(src, define):
