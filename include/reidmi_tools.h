@@ -46,6 +46,46 @@ int reidmi_gemm_f16_qkv(const void* A, int64_t lda, const void* W, int64_t ldw, 
                         const float* bias, const void* rowstat, const float* colsum, void* q, void* k, void* vt,
                         int lpad, void* stream);
 
+/* reidmi_gemm_f16_qkv for columns [n_off, n_off + N) of [q | k | v] (n_off a multiple of 64; W, bias
+ * and colsum point at the first of them) with an explicit tiling (tile, ngroups: as
+ * reidmi_gemm_f16_tiled).  The outputs of column blocks the GEMM does not produce may be NULL:
+ * n_off = H*64, N = 2*H*64 is the K / V-only GEMM, L = 1 with lpad = 1 and lda = the sequence stride
+ * the CLS-query GEMM of the encoder's last block. */
+int reidmi_gemm_f16_qkv_ex(const void* A, int64_t lda, const void* W, int64_t ldw, int64_t nseq, int L, int H,
+                           int64_t N, int64_t n_off, const float* bias, const void* rowstat, const float* colsum,
+                           void* q, void* k, void* vt, int lpad, int tile, int ngroups, void* stream);
+
+/* The pieces of reidmi_vit_forward / reidmi_text_forward between their GEMMs, each through the
+ * launcher its tower runs.
+ *
+ * Patch columns: images [B][3][H][Wimg] (fp32, or fp16 with images_f16) -> col [B*gh*gw][kpad] fp16,
+ * column c*patch^2 + ky*patch + kx, zero from 3*patch^2 on; tta (nullable) [B][2] = (top, left) of the
+ * augmented view (flip, Pad((10,5)), crop).  The compile-time patch sizes (16, 14) run when kpad is
+ * the packed round_up(3*patch^2, 64), else the runtime-patch kernel. */
+int reidmi_im2col_f16(const void* images, int images_f16, int64_t B, int H, int Wimg, int patch, int stride, int gh,
+                      int gw, int kpad, const int32_t* tta, void* col, void* stream);
+
+/* Patch embed: x [B*L][W] fp16, L = 1 + NP + n_ctx: x[b*L+1+p] = col[b*NP+p] . conv_w^T + pos_emb[1+p]
+ * (the conv1 GEMM's epilogue; conv_w [W][kpad] fp16, tile as reidmi_gemm_f16_tiled), x[b*L] =
+ * class_emb + pos_emb[0], x[b*L+1+NP+i] = vpt[i]. */
+int reidmi_patch_embed_f16(const void* col, const void* conv_w, const float* pos_emb, const float* class_emb,
+                           const float* vpt, int n_ctx, int64_t B, int NP, int W, int kpad, void* x, int tile,
+                           void* stream);
+
+/* reidmi_layernorm on fp16 rows (the towers' residual stream; W in 512, 768, 1024): output row r
+ * is LayerNorm(x[row_idx ? row_idx[r] : r]), written to any of y32 (fp32), y16 and yh (fp16; yh may
+ * be x itself, the in-place ln_pre); sto (nullable, needs yh) [rows][2] receives (rstd, -mean*rstd)
+ * of the fp16 rows written to yh, the bits reidmi_row_stats_f16 gives on them. */
+int reidmi_layernorm_f16(const void* x, int64_t rows, int64_t ldx, const int32_t* row_idx, int64_t W,
+                         const float* gamma, const float* beta, float eps, float* y32, int64_t ldy32, void* y16,
+                         int64_t ldy16, void* yh, int64_t ldyh, void* sto, void* stream);
+
+/* Text embed: x [N*L][W] fp16, x[n*L+t] = half((prompts ? prompts[n][t] : tok_emb[tokens[n][t]]) +
+ * pos_emb[t]) for the first L of the Lt positions of tokens [N][Lt] (int64) / prompts [N][Lt][W];
+ * rows[n] = n*L + min(argmax(tokens[n]) over all Lt positions (first maximum), L-1). */
+int reidmi_text_embed_f16(const int64_t* tokens, const float* prompts, const float* tok_emb, const float* pos_emb,
+                          int64_t N, int L, int Lt, int W, int64_t vocab, void* x, int32_t* rows, void* stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -324,6 +324,38 @@ __global__ __launch_bounds__(256) void im2col_kernel(const TI* __restrict__ img,
     }
 }
 
+// col [B*gh*gw][kpad] <- the patches of images [B][3][H][Wimg] (fp32, or fp16 with images_f16),
+// through the TTA view when tta [B][2] (top i, left j) is given.
+static int im2col(const void* images, int images_f16, int64_t B, int H, int Wimg, int patch, int stride, int gh,
+                  int gw, int kpad, const int32_t* tta, _Float16* col, hipStream_t s) {
+    RM_REQUIRE(patch > 0 && stride > 0 && gh > 0 && gw > 0 && (gh - 1) * stride + patch <= H &&
+                   (gw - 1) * stride + patch <= Wimg,
+               "im2col: the patch grid does not fit the image");
+    RM_REQUIRE(kpad % 8 == 0 && kpad >= 3 * patch * patch, "im2col: kpad");
+    RM_REQUIRE(B * gh < (1ll << 31) && Wimg % 8 == 0, "vit: im2col needs B * grid_h < 2^31 and width % 8 == 0");
+    if (B == 0) return OK;
+    const dim3 g((unsigned)(B * gh)), t(256);
+    const size_t lds = (size_t)3 * patch * Wimg * sizeof(_Float16);
+    RM_REQUIRE(lds <= 64 * 1024, "vit: image too wide for the im2col row stage");
+#define RM_IM2COL(TI, PT)                                                                                       \
+    hipLaunchKernelGGL((im2col_kernel<TI, PT>), g, t, lds, s, (const TI*)images, H, Wimg, patch, stride, gh, gw, \
+                       kpad, tta, col)
+    // the compile-time patch sizes assume the packed kpad (pack.hip)
+    const int pt = kpad == (3 * patch * patch + 63) / 64 * 64 ? patch : 0;
+    if (images_f16) {
+        if (pt == 16) RM_IM2COL(_Float16, 16);
+        else if (pt == 14) RM_IM2COL(_Float16, 14);
+        else RM_IM2COL(_Float16, 0);
+    } else {
+        if (pt == 16) RM_IM2COL(float, 16);
+        else if (pt == 14) RM_IM2COL(float, 14);
+        else RM_IM2COL(float, 0);
+    }
+#undef RM_IM2COL
+    RM_LAUNCHED();
+    return OK;
+}
+
 // x[b*L+0] = class_emb + pos[0]; IVLP: x[b*L+1+NP+i] = half(vpt[i]) (maple.py:765-767).
 __global__ void cls_rows_kernel(_Float16* __restrict__ x, int64_t B, int L, int W, const float* __restrict__ cls,
                                 const float* __restrict__ pos, int NP, int n_ctx, const float* __restrict__ vpt) {
@@ -336,6 +368,28 @@ __global__ void cls_rows_kernel(_Float16* __restrict__ x, int64_t B, int L, int 
     const int r = (int)(br % rows);
     if (r == 0) x[(b * L) * W + n] = (_Float16)(cls[n] + pos[n]);
     else x[(b * L + 1 + NP + (r - 1)) * W + n] = (_Float16)vpt[(r - 1) * W + n];
+}
+
+// Patch embed of B images on the residual stream x [B*L][W], L = 1 + NP + n_ctx: the conv1 GEMM
+// with the positional embedding in its epilogue (patch rows), then the CLS / VPT rows.
+static int patch_embed(const _Float16* col, const void* conv_w, const float* pos_emb, const float* class_emb,
+                       const float* vpt, int n_ctx, int64_t B, int NP, int W, int kpad, _Float16* x, hipStream_t s,
+                       const GemmOpts& opt = GemmOpts{}) {
+    RM_REQUIRE(n_ctx == 0 || vpt != nullptr, "vit: n_ctx > 0 needs vpt");
+    const int L = 1 + NP + n_ctx;
+    int rc;
+    EpiArgs ep{};
+    ep.out = x;
+    ep.ldc = W;
+    ep.pos = pos_emb;
+    ep.npatch = NP;
+    ep.seq = L;
+    if ((rc = gemm_f16(EPI_PATCH, col, kpad, conv_w, kpad, B * NP, W, kpad, ep, s, opt))) return rc;
+    const int64_t ce = B * (1 + n_ctx) * W;
+    hipLaunchKernelGGL(cls_rows_kernel, dim3(ceil_div(ce, 256)), dim3(256), 0, s, x, B, L, W, class_emb, pos_emb, NP,
+                       n_ctx, vpt);
+    RM_LAUNCHED();
+    return OK;
 }
 
 // IVLP per-block prompt: rows [row0, row0+n_ctx) of every sequence <- half(prompt)
@@ -386,6 +440,21 @@ __global__ void eot_rows_kernel(const int64_t* __restrict__ tokens, int64_t N, i
     for (int i = 1; i < Lt; i++)
         if (t[i] > bv) { bv = t[i]; best = i; }
     rows[n] = (int32_t)(n * L + (best < L ? best : L - 1));
+}
+
+static int text_embed(_Float16* x, const int64_t* tokens, const float* prompts, const float* tok_emb, const float* pos,
+                      int64_t N, int L, int Lt, int W, int64_t vocab, hipStream_t s) {
+    const int64_t te = N * L * (W / 4);
+    hipLaunchKernelGGL(text_embed_kernel, dim3(ceil_div(te, 256)), dim3(256), 0, s, x, tokens, prompts, tok_emb, pos, N,
+                       L, Lt, W, vocab);
+    RM_LAUNCHED();
+    return OK;
+}
+
+static int eot_rows(const int64_t* tokens, int64_t N, int L, int Lt, int32_t* rows, hipStream_t s) {
+    hipLaunchKernelGGL(eot_rows_kernel, dim3(ceil_div(N, 256)), dim3(256), 0, s, tokens, N, L, Lt, rows);
+    RM_LAUNCHED();
+    return OK;
 }
 
 // --------------------------------------------------------------- workspace plan
@@ -614,40 +683,10 @@ REIDMI_API int reidmi_vit_forward(const reidmi_vit_weights* w, const void* image
     _Float16* col = (_Float16*)(ws + P.u);
     const int64_t M = B * L;
     // patch embed (+pos), CLS/VPT rows, ln_pre
-    RM_REQUIRE(B * w->grid_h < (1ll << 31) && Wimg % 8 == 0, "vit: im2col needs B * grid_h < 2^31 and width % 8 == 0");
-    {
-        const dim3 g((unsigned)(B * w->grid_h)), t(256);
-        const size_t lds = (size_t)3 * w->patch * Wimg * sizeof(_Float16);
-        RM_REQUIRE(lds <= 64 * 1024, "vit: image too wide for the im2col row stage");
-#define RM_IM2COL(TI, PT)                                                                                      \
-    hipLaunchKernelGGL((im2col_kernel<TI, PT>), g, t, lds, s, (const TI*)images, H, Wimg, w->patch, w->stride, \
-                       w->grid_h, w->grid_w, w->kpad, tta, col)
-        // the compile-time patch sizes assume the packed kpad (pack.hip)
-        const int pt = w->kpad == (3 * w->patch * w->patch + 63) / 64 * 64 ? w->patch : 0;
-        if (images_f16) {
-            if (pt == 16) RM_IM2COL(_Float16, 16);
-            else if (pt == 14) RM_IM2COL(_Float16, 14);
-            else RM_IM2COL(_Float16, 0);
-        } else {
-            if (pt == 16) RM_IM2COL(float, 16);
-            else if (pt == 14) RM_IM2COL(float, 14);
-            else RM_IM2COL(float, 0);
-        }
-#undef RM_IM2COL
-    }
-    RM_LAUNCHED();
-    EpiArgs ep{};
-    ep.out = x;
-    ep.ldc = W;
-    ep.pos = w->pos_emb;
-    ep.npatch = NP;
-    ep.seq = L;
-    if ((rc = gemm_f16(EPI_PATCH, col, w->kpad, w->conv_w, w->kpad, B * NP, W, w->kpad, ep, s))) return rc;
-    RM_REQUIRE(w->n_ctx == 0 || w->vpt != nullptr, "vit: n_ctx > 0 needs vpt");
-    const int64_t ce = B * (1 + w->n_ctx) * W;
-    hipLaunchKernelGGL(cls_rows_kernel, dim3(ceil_div(ce, 256)), dim3(256), 0, s, x, B, L, W, w->class_emb,
-                       w->pos_emb, NP, w->n_ctx, w->vpt);
-    RM_LAUNCHED();
+    if ((rc = im2col(images, images_f16, B, H, Wimg, w->patch, w->stride, w->grid_h, w->grid_w, w->kpad, tta, col, s)))
+        return rc;
+    if ((rc = patch_embed(col, w->conv_w, w->pos_emb, w->class_emb, w->vpt, w->n_ctx, B, NP, W, w->kpad, x, s)))
+        return rc;
     // in place; also writes the statistics of its output rows, block 0's ln_1 (XS_READY)
     if ((rc = layernorm(x, M, W, nullptr, W, w->ln_pre_w, w->ln_pre_b, 1e-5f, nullptr, 0, nullptr, 0, s, x, W, nullptr,
                         (float2*)(ws + P.st))))
@@ -710,11 +749,8 @@ REIDMI_API int reidmi_text_forward(const reidmi_text_weights* w, const int64_t* 
     _Float16* x = (_Float16*)(ws + P.x);
     _Float16* h = (_Float16*)(ws + P.h);
     int32_t* rows = (int32_t*)(ws + P.rows);
-    const int64_t te = N * L * (W / 4);
-    hipLaunchKernelGGL(text_embed_kernel, dim3(ceil_div(te, 256)), dim3(256), 0, s, x, tokens, prompts, w->tok_emb,
-                       w->pos_emb, N, L, Lt, W, (int64_t)w->vocab);
-    RM_LAUNCHED();
     int rc;
+    if ((rc = text_embed(x, tokens, prompts, w->tok_emb, w->pos_emb, N, L, Lt, W, (int64_t)w->vocab, s))) return rc;
     for (int i = 0; i < w->layers; i++) {
         const reidmi_block_weights& bw = w->blocks[i];
         if (i > 0 && bw.prompt && w->n_ctx > 0) {
@@ -726,8 +762,7 @@ REIDMI_API int reidmi_text_forward(const reidmi_text_weights* w, const int64_t* 
         const XStats xs = i > 0 && !(bw.prompt && w->n_ctx > 0) ? XS_PARTIALS : XS_ROWS;
         if ((rc = run_block(bw, ws, P, N, L, W, w->heads, true, xs, s))) return rc;
     }
-    hipLaunchKernelGGL(eot_rows_kernel, dim3(ceil_div(N, 256)), dim3(256), 0, s, tokens, N, L, Lt, rows);
-    RM_LAUNCHED();
+    if ((rc = eot_rows(tokens, N, L, Lt, rows, s))) return rc;
     if ((rc = layernorm(x, N, W, rows, W, w->ln_final_w, w->ln_final_b, 1e-5f, nullptr, 0, h, W, s))) return rc;
     EpiArgs eo{};
     eo.out = out;
@@ -761,3 +796,46 @@ REIDMI_API int reidmi_gemm_f16_resid_partials(const void* A, int64_t lda, const 
     return gemm_f16(EPI_RESID_F16, (const _Float16*)A, lda, (const _Float16*)Wt, ldw, M, (int)N, (int)K, e,
                     (hipStream_t)stream);
 }
+
+#ifdef REIDMI_TOOLS
+// The towers' layout kernels one at a time (tests; tools library, include/reidmi_tools.h): each
+// runs the helper its tower runs.
+REIDMI_API int reidmi_im2col_f16(const void* images, int images_f16, int64_t B, int H, int Wimg, int patch, int stride,
+                                 int gh, int gw, int kpad, const int32_t* tta, void* col, void* stream) {
+    RM_REQUIRE(images && col && B >= 0 && H > 0 && Wimg > 0, "im2col: null argument or bad shape");
+    return im2col(images, images_f16, B, H, Wimg, patch, stride, gh, gw, kpad, tta, (_Float16*)col,
+                  (hipStream_t)stream);
+}
+
+REIDMI_API int reidmi_patch_embed_f16(const void* col, const void* conv_w, const float* pos_emb,
+                                      const float* class_emb, const float* vpt, int n_ctx, int64_t B, int NP, int W,
+                                      int kpad, void* x, int tile, void* stream) {
+    RM_REQUIRE(col && conv_w && pos_emb && class_emb && x && n_ctx >= 0 && B >= 0 && NP > 0 && W > 0,
+               "patch_embed: null argument or bad shape");
+    if (B == 0) return OK;
+    GemmOpts opt;
+    opt.tile = tile;
+    return patch_embed((const _Float16*)col, conv_w, pos_emb, class_emb, vpt, n_ctx, B, NP, W, kpad, (_Float16*)x,
+                       (hipStream_t)stream, opt);
+}
+
+REIDMI_API int reidmi_layernorm_f16(const void* x, int64_t rows, int64_t ldx, const int32_t* row_idx, int64_t W,
+                                    const float* gamma, const float* beta, float eps, float* y32, int64_t ldy32,
+                                    void* y16, int64_t ldy16, void* yh, int64_t ldyh, void* sto, void* stream) {
+    RM_REQUIRE(x && gamma && beta && rows >= 0, "layernorm_f16: null argument");
+    return layernorm((const _Float16*)x, rows, ldx, row_idx, W, gamma, beta, eps, y32, ldy32, (_Float16*)y16, ldy16,
+                     (hipStream_t)stream, (_Float16*)yh, ldyh, nullptr, (float2*)sto);
+}
+
+REIDMI_API int reidmi_text_embed_f16(const int64_t* tokens, const float* prompts, const float* tok_emb,
+                                     const float* pos_emb, int64_t N, int L, int Lt, int W, int64_t vocab, void* x,
+                                     int32_t* rows, void* stream) {
+    RM_REQUIRE(tokens && (prompts || tok_emb) && pos_emb && x && rows, "text_embed: null argument");
+    RM_REQUIRE(N >= 0 && L > 0 && L <= Lt && W > 0 && W % 4 == 0 && vocab > 0, "text_embed: bad shape");
+    if (N == 0) return OK;
+    int rc;
+    if ((rc = text_embed((_Float16*)x, tokens, prompts, tok_emb, pos_emb, N, L, Lt, W, vocab, (hipStream_t)stream)))
+        return rc;
+    return eot_rows(tokens, N, L, Lt, rows, (hipStream_t)stream);
+}
+#endif  // REIDMI_TOOLS

@@ -1573,10 +1573,16 @@ REIDMI_API int reidmi_gemm_f16_tiled(int epi, const void* A, int64_t lda, const 
 }
 
 // The QKV GEMM alone (EPI_QKV: ln_1 fold + head split into q, k [nseq*H][L][64] and
-// v^T [nseq*H][64][lpad]), for pricing its epilogue against a plain fp16 output (tools/lib_ab.py)
-REIDMI_API int reidmi_gemm_f16_qkv(const void* A, int64_t lda, const void* W, int64_t ldw, int64_t nseq, int L, int H,
-                                   const float* bias, const void* rowstat, const float* colsum, void* q, void* k,
-                                   void* vt, int lpad, void* stream) {
+// v^T [nseq*H][64][lpad]): columns [n_off, n_off + N) of [q | k | v] (W, bias and colsum point at
+// the first of them, as run_block_cls passes them), with the tiling of opt
+static int qkv_api(const void* A, int64_t lda, const void* W, int64_t ldw, int64_t nseq, int L, int H, int64_t N,
+                   int64_t n_off, const float* bias, const void* rowstat, const float* colsum, void* q, void* k,
+                   void* vt, int lpad, const GemmOpts& opt, void* stream) {
+    const int64_t wd = (int64_t)H * 64;
+    RM_REQUIRE(nseq >= 0 && L > 0 && H > 0 && lpad >= L, "gemm_f16_qkv: bad shape");
+    RM_REQUIRE(N > 0 && n_off >= 0 && n_off % 64 == 0 && n_off + N <= 3 * wd, "gemm_f16_qkv: columns outside [q | k | v]");
+    RM_REQUIRE((q || n_off >= wd) && (k || n_off >= 2 * wd || n_off + N <= wd) && (vt || n_off + N <= 2 * wd),
+               "gemm_f16_qkv: null output for a produced column block");
     EpiArgs ea{};
     ea.bias = bias;
     ea.rowstat = (const float2*)rowstat;
@@ -1587,6 +1593,27 @@ REIDMI_API int reidmi_gemm_f16_qkv(const void* A, int64_t lda, const void* W, in
     ea.seq = L;
     ea.heads = H;
     ea.lpad = lpad;
-    return gemm_f16(EPI_QKV, A, lda, W, ldw, nseq * L, 3 * (int64_t)H * 64, H * 64, ea, (hipStream_t)stream);
+    ea.n_off = (int)n_off;
+    return gemm_f16(EPI_QKV, A, lda, W, ldw, nseq * L, N, wd, ea, (hipStream_t)stream, opt);
+}
+
+// ... the whole [q | k | v], automatic tiling, for pricing its epilogue against a plain fp16
+// output (tools/lib_ab.py)
+REIDMI_API int reidmi_gemm_f16_qkv(const void* A, int64_t lda, const void* W, int64_t ldw, int64_t nseq, int L, int H,
+                                   const float* bias, const void* rowstat, const float* colsum, void* q, void* k,
+                                   void* vt, int lpad, void* stream) {
+    return qkv_api(A, lda, W, ldw, nseq, L, H, 3 * (int64_t)H * 64, 0, bias, rowstat, colsum, q, k, vt, lpad,
+                   GemmOpts{}, stream);
+}
+
+// ... any column range and a forced tiling (tests: the K / V-only and CLS-query forms of run_block_cls)
+REIDMI_API int reidmi_gemm_f16_qkv_ex(const void* A, int64_t lda, const void* W, int64_t ldw, int64_t nseq, int L,
+                                      int H, int64_t N, int64_t n_off, const float* bias, const void* rowstat,
+                                      const float* colsum, void* q, void* k, void* vt, int lpad, int tile, int ngroups,
+                                      void* stream) {
+    GemmOpts opt;
+    opt.tile = tile;
+    opt.ngroups = ngroups;
+    return qkv_api(A, lda, W, ldw, nseq, L, H, N, n_off, bias, rowstat, colsum, q, k, vt, lpad, opt, stream);
 }
 #endif  // REIDMI_TOOLS

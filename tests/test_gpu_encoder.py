@@ -67,6 +67,43 @@ def test_gemm_epilogues(gpu, epi, M, N, K):
     assert (got - ref).abs().max() <= tol * (ref.abs().max() + 1)
 
 
+@pytest.mark.parametrize("has_bias", [True, False])
+@pytest.mark.parametrize("epi", [0, 1, 5, 6])
+@pytest.mark.parametrize("M,N,K", [(37, 256, 256), (1, 128, 64)])
+def test_gemm_strided_operands(gpu, epi, M, N, K, has_bias):
+    """Row strides beyond the row length, as run_block_cls passes them (the CLS row of each
+    sequence: lda = ldc = L * W): lda = 5 K, ldc = 3 N.  Every written element has the bits of the
+    contiguous call, the elements between rows (NaN in A, a fill value in out) are neither read
+    into the result nor written, with and without a bias, on both tiles where the shape admits
+    the persistent one."""
+    L = _lib()
+    g = torch.Generator().manual_seed(M + N + K + epi)
+    A = torch.randn(M, K, generator=g).half()
+    W = (torch.randn(N, K, generator=g) / K ** 0.5).half().cuda()
+    bias = torch.randn(N, generator=g).cuda() if has_bias else None
+    base = torch.randn(M, N, generator=g).half()
+    dt = torch.float32 if epi == 5 else torch.float16
+    lda, ldc, fill, guard = 5 * K, 3 * N, -1234.0, 4096
+    As = torch.full((M, lda), float("nan"), dtype=torch.float16)
+    As[:, :K] = A
+    As, Ac = As.cuda(), A.cuda()
+    for tile in (1, 2) if N % 256 == 0 and K >= 128 else (1,):
+        flat = torch.full((M * ldc + guard,), fill, dtype=dt, device="cuda")
+        outs = flat[:M * ldc].view(M, ldc)
+        outc = torch.full((M, N), fill, dtype=dt, device="cuda")
+        if epi == 6:
+            outs[:, :N] = base.cuda()
+            outc.copy_(base)
+        L.call_tools("reidmi_gemm_f16_tiled", epi, L.ptr(Ac), K, L.ptr(W), K, M, N, K, L.ptr(bias), None, None,
+                     L.ptr(outc), N, tile, 0, L.stream())
+        L.call_tools("reidmi_gemm_f16_tiled", epi, L.ptr(As), lda, L.ptr(W), K, M, N, K, L.ptr(bias), None, None,
+                     L.ptr(outs), ldc, tile, 0, L.stream())
+        torch.cuda.synchronize()
+        assert torch.isfinite(outc).all() and not (outc == fill).any()
+        assert torch.equal(outs[:, :N], outc), tile
+        assert (outs[:, N:] == fill).all() and (flat[M * ldc:] == fill).all(), tile
+
+
 @pytest.mark.parametrize("epi", [0, 1, 5, 6])
 @pytest.mark.parametrize("M,N,K", [(54016, 768, 768), (1000, 2304, 768), (700, 512, 3072), (70000, 256, 192),
                                    (40000, 3072, 768)])
