@@ -40,6 +40,27 @@ int reidmi_gemm_f16_w4(const void* A, int64_t lda, const void* W, int64_t ldw, i
 int reidmi_mhsa_f16_rr(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H,
                        void* stream);
 
+/* The single-query (CLS) attention of the last block's K / V path (mhsa_cls_kernel, one wave per
+ * (sequence, head)): q [nseq*H][64] fp16 (the CLS rows), k [nseq*H][L][64] and vt [nseq*H][64][lpad]
+ * as reidmi_mhsa_f16 takes them (lpad = reidmi_attn_lpad(L); columns >= L are never used, though
+ * the 8-element piece holding column L-1 is read whole), 1 <= L <= 256 -> o [nseq][H*64] fp16. */
+int reidmi_mhsa_cls_f16(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H,
+                        void* stream);
+
+/* The last block's CLS attention without K and V (cls_u_kernel, cls_attn_kernel, cls_o_kernel;
+ * attention.hip): x [nseq*L][W] fp16 (the block's ln_1 input), rs [nseq*L][2] fp32 = (rstd, -mean
+ * rstd) of its rows (reidmi_row_stats_f16), q [nseq][W] fp16 (the CLS queries, head-major), wqkv
+ * [3W][W] fp16 / colsum [3W] / bias [3W] the ln_1-folded in_proj -> o [nseq][W] fp16.  W is 768 or
+ * 1024 with H = W / 64, 1 <= L <= 224; nseq = 0 is a no-op.  Neither x nor rs needs padding: rows
+ * past L of the last 32-token chunk re-read row L-1 of x (weight 0) and read no rs, images past
+ * nseq of the last group of 16 re-read image nseq-1 and are not stored.  ws holds u, the score
+ * constants, z and alpha: at least reidmi_cls_attn_nokv_ws_bytes(nseq, W) bytes (ws_bytes, checked),
+ * 256-byte aligned. */
+int64_t reidmi_cls_attn_nokv_ws_bytes(int64_t nseq, int W);
+int reidmi_cls_attn_nokv_f16(const void* x, const void* rs, const void* q, const void* wqkv, const float* colsum,
+                             const float* bias, int64_t nseq, int L, int H, int W, void* ws, int64_t ws_bytes, void* o,
+                             void* stream);
+
 /* The QKV GEMM alone (ln_1 fold + the head split reidmi_vit_forward uses): x [nseq*L][lda],
  * W [3*H*64][ldw] -> q, k [nseq*H][L][64], vt [nseq*H][64][lpad] (lpad = reidmi_attn_lpad(L)). */
 int reidmi_gemm_f16_qkv(const void* A, int64_t lda, const void* W, int64_t ldw, int64_t nseq, int L, int H,

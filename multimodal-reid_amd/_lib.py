@@ -103,6 +103,9 @@ TOOLS_SIGNATURES = {
     "reidmi_gemm_f16_w4": [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _i32, _vp],
     "reidmi_gemm_f16_qkv": [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp],
     "reidmi_mhsa_f16_rr": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp],
+    "reidmi_mhsa_cls_f16": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp],
+    "reidmi_cls_attn_nokv_ws_bytes": [_i64, _i32],
+    "reidmi_cls_attn_nokv_f16": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp],
     "reidmi_gemm_f16_qkv_ex": [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32,
                                _i32, _i32, _vp],
     "reidmi_im2col_f16": [_vp, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp],

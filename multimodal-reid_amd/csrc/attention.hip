@@ -1404,4 +1404,21 @@ REIDMI_API int reidmi_mhsa_f16_rr(const void* q, const void* k, const void* vt, 
     RM_REQUIRE(L >= kRrLmin && L <= kRrVS && nseq * H < (1ll << 31), "reidmi_mhsa_f16_rr: 205 <= L <= 212");
     return launch_mhsa_rr(q, k, vt, o, nseq, L, H, (hipStream_t)stream);
 }
+
+// The two CLS attentions of the encoder's last block (run_block_cls), each through its own host
+// launcher, so tests/test_gpu_attention.py can compare them with fp64 at any length and batch.
+REIDMI_API int reidmi_mhsa_cls_f16(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H,
+                                   void* stream) {
+    return mhsa_cls(q, k, vt, o, nseq, L, H, (hipStream_t)stream);
+}
+
+REIDMI_API int64_t reidmi_cls_attn_nokv_ws_bytes(int64_t nseq, int W) { return cls_attn_nokv_ws_bytes(nseq, W); }
+
+REIDMI_API int reidmi_cls_attn_nokv_f16(const void* x, const void* rs, const void* q, const void* wqkv,
+                                        const float* colsum, const float* bias, int64_t nseq, int L, int H, int W,
+                                        void* ws, int64_t ws_bytes, void* o, void* stream) {
+    RM_REQUIRE(nseq <= 0 || ws_bytes >= cls_attn_nokv_ws_bytes(nseq, W),
+               "reidmi_cls_attn_nokv_f16: workspace smaller than reidmi_cls_attn_nokv_ws_bytes");
+    return cls_attn_nokv(x, rs, q, wqkv, colsum, bias, nseq, L, H, W, ws, o, (hipStream_t)stream);
+}
 #endif

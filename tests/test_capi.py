@@ -112,3 +112,59 @@ def test_counted_wait_kernels_use_no_scratch(src, kernels):
             seen += 1
             assert int(m.group(1)) == 0, f"{name} spills to scratch ({m.group(1)} bytes/lane)"
     assert seen >= 3, r.stderr[-2000:]
+
+
+# ---- argument checks of the attention entry points: each returns before any HIP call, so they
+# run here with null pointers and no GPU
+def _tools():
+    from multimodal_reid_amd import _lib
+    return _lib.load_tools()
+
+
+def _refused(T, rc):
+    return rc != 0 and len(T.reidmi_last_error()) > 0
+
+
+def test_attn_lpad_every_length():
+    T = _tools()
+    for L in range(1, 257):
+        assert T.reidmi_attn_lpad(L) == 32 * -(-L // 32) + 4, L
+    for L in (0, -1, 257):
+        assert T.reidmi_attn_lpad(L) < 0, L
+
+
+@pytest.mark.parametrize("L", [0, 257])
+@pytest.mark.parametrize("causal", [0, 1])
+def test_mhsa_refuses_unsupported_lengths(L, causal):
+    T = _tools()
+    assert _refused(T, T.reidmi_mhsa_f16(None, None, None, None, 2, L, 3, causal, None))
+    assert b"mhsa" in T.reidmi_last_error()
+
+
+@pytest.mark.parametrize("L", [204, 213])
+def test_mhsa_rr_refuses_lengths_outside_its_range(L):
+    T = _tools()
+    assert _refused(T, T.reidmi_mhsa_f16_rr(None, None, None, None, 2, L, 3, None))
+    assert b"reidmi_mhsa_f16_rr" in T.reidmi_last_error()
+
+
+@pytest.mark.parametrize("L,H,W,what", [(211, 8, 512, b"width"), (211, 12, 1024, b"width"), (211, 16, 768, b"width"),
+                                        (0, 12, 768, b"<= L"), (225, 12, 768, b"<= L"), (225, 16, 1024, b"<= L")])
+def test_cls_attn_nokv_refuses_unsupported_shapes(L, H, W, what):
+    T = _tools()
+    big = 1 << 40  # (the workspace is not what is refused)
+    assert _refused(T, T.reidmi_cls_attn_nokv_f16(None, None, None, None, None, None, 4, L, H, W, None, big, None, None))
+    assert what in T.reidmi_last_error(), T.reidmi_last_error()
+
+
+def test_cls_attn_nokv_workspace_size_and_empty_batch():
+    T = _tools()
+    for W in (768, 1024):
+        H = W // 64
+        assert T.reidmi_cls_attn_nokv_f16(None, None, None, None, None, None, 0, 211, H, W, None, 0, None, None) == 0
+        need = T.reidmi_cls_attn_nokv_ws_bytes(37, W)
+        # u (fp16 hi, lo), the score constants, z and alpha of 37 images, each rounded up to 256 bytes
+        assert need >= 37 * (2 * H * W * 2 + 32 * 4 + H * W * 4 + H * 4) and need % 256 == 0
+        assert _refused(T, T.reidmi_cls_attn_nokv_f16(None, None, None, None, None, None, 37, 211, H, W, None,
+                                                      need - 1, None, None))
+        assert b"workspace" in T.reidmi_last_error()
