@@ -70,6 +70,28 @@ int reidmi_cosine_f32(const float* q, int64_t Q, int64_t ldq, const float* g, in
 int reidmi_topk_rows_f32(const float* x, int64_t rows, int64_t cols, int64_t ldx, const float* row_div, int k,
                          int32_t* out_idx, float* out_val, int64_t ldo, void* stream);
 
+/* Ranked retrieval: the k nearest gallery rows of every query row, without a Q x G matrix.
+ * out_idx[i*ldo + 0..k) / out_dist[i*ldo + 0..k) (out_dist nullable) are, bit for bit, what
+ * reidmi_distmat_f32 followed by reidmi_topk_rows_f32(k, row_div = NULL) gives on the same
+ * inputs: the same fp32 distances, ascending, ties by gallery index.  The selection runs in the
+ * distance kernel's epilogue; the gallery is cut into ranges (a pure function of Q, G, k) whose
+ * partial lists a small kernel merges.
+ * Labels: all four arrays or none.  With labels, gallery item j is skipped for query i when
+ * g_pids[j] == q_pids[i] && g_cams[j] == q_cams[i] (evaluate.py:46-48), and a row with fewer
+ * than k items left is padded with index -1 and distance +inf.
+ * 1 <= k <= min(G, 128); a larger k is refused (reidmi_distmat_f32 + reidmi_topk_rows_f32 is
+ * the route).  Features must be finite.  Any D, ldq, ldg and alignment reidmi_distmat_f32
+ * accepts (rows that are not 16-byte aligned, or D % 4 != 0, run the single-stage mainloop).
+ * ws: reidmi_search_workspace_bytes(Q, G, D, k) bytes, 16-byte aligned (the squared norms and
+ * the ranges' candidate lists: 8 * 128 * ceil(Q / 128) * ranges * cap bytes, cap = 256 for
+ * k <= 64, else 384, at most 1024 lists of 128 rows unless Q > 131072; ws_bytes is checked).
+ * No allocation or synchronisation inside. */
+int64_t reidmi_search_workspace_bytes(int64_t Q, int64_t G, int64_t D, int k);
+int reidmi_search_f32(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G, int64_t ldg, int64_t D,
+                      int k, const int64_t* q_pids, const int64_t* q_cams, const int64_t* g_pids,
+                      const int64_t* g_cams, int32_t* out_idx, float* out_dist, int64_t ldo, void* ws,
+                      int64_t ws_bytes, void* stream);
+
 /* Per-query part of eval_func — evaluate.py:40-80.  For query q: valid[q] (any match kept),
  * first[q] (0-based kept-rank of the first match), ap[q] (float64 AP exactly as numpy sums
  * it), nkept[q] (gallery items left after same-pid-same-cam removal).  No capacity limit

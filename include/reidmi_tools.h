@@ -19,6 +19,20 @@ extern "C" {
 int reidmi_distmat_f32_variant(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G, int64_t ldg,
                                int64_t D, float* out, int64_t ldo, float* ws, int variant, void* stream);
 
+/* reidmi_search_f32 with a forced number of gallery ranges (splits: 1..min(G, 4096), ranges of
+ * ceil(G / splits) columns, tile-aligned or not; 0 = the launcher's choice) and a forced
+ * candidate-list capacity per row (k + 128 <= cap <= 512; 0 = the launcher's choice), so that
+ * tests can make rows overflow and compact.  Every choice gives the same lists.  stats
+ * (nullable, device int32[2], added to: zero it first): [0] the compactions a full list forced
+ * (the one that sets a row's first threshold once it holds k candidates is not counted, nor the
+ * final one), [1] the (distance, index) pairs the filter kept.  ws: at least
+ * reidmi_search_ex_workspace_bytes(Q, G, D, k, splits, cap) bytes. */
+int64_t reidmi_search_ex_workspace_bytes(int64_t Q, int64_t G, int64_t D, int k, int splits, int cap);
+int reidmi_search_f32_ex(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G, int64_t ldg, int64_t D,
+                         int k, const int64_t* q_pids, const int64_t* q_cams, const int64_t* g_pids,
+                         const int64_t* g_cams, int32_t* out_idx, float* out_dist, int64_t ldo, void* ws,
+                         int64_t ws_bytes, int splits, int cap, int32_t* stats, void* stream);
+
 /* reidmi_gemm_f16 with an explicit tiling: tile 0 = auto (the persistent 256x256x64 LDS-DMA
  * tile for >= 256 tiles, else 128x128x64), 1 = force 128x128, 2 = force persistent; ngroups =
  * the persistent walk's XCD groups (1, 2, 4, 8; each owns 1/ngroups of the N-tiles), 0 = auto.

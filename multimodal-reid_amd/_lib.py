@@ -30,6 +30,9 @@ SIGNATURES = {
     "reidmi_distmat_f16_workspace_bytes": [_i64, _i64, _i64],
     "reidmi_distmat_f16": [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp],
     "reidmi_topk_rows_f32": [_vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _i64, _vp],
+    "reidmi_search_workspace_bytes": [_i64, _i64, _i64, _i32],
+    "reidmi_search_f32": [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64,
+                          _vp],
     "reidmi_eval_rows": [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
     "reidmi_eval_rows_workspace_bytes": [_i64],
     "reidmi_gemm_f16": [_i32, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp],
@@ -99,6 +102,9 @@ SIGNATURES = {
 # libreidmi_tools.so only (include/reidmi_tools.h): forced kernel variants for tests / A-B timing
 TOOLS_SIGNATURES = {
     "reidmi_distmat_f32_variant": [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i32, _vp],
+    "reidmi_search_ex_workspace_bytes": [_i64, _i64, _i64, _i32, _i32, _i32],
+    "reidmi_search_f32_ex": [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp,
+                             _i64, _i32, _i32, _vp, _vp],
     "reidmi_gemm_f16_tiled": [_i32, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp],
     "reidmi_gemm_f16_w4": [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _i32, _vp],
     "reidmi_gemm_f16_qkv": [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp],

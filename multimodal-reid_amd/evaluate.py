@@ -83,6 +83,37 @@ def topk_rows_device(x, k, row_div=None, with_values=False):
     return (idx, val) if with_values else idx
 
 
+def search_device(qf, gf, k, q_pids=None, q_camids=None, g_pids=None, g_camids=None, with_dist=True):
+    """The k nearest gallery rows of every query row (reidmi_search_f32: the selection runs in the
+    distance kernel's epilogue, no (Q,G) matrix): (idx int32 [Q][k], dist fp32 [Q][k] or None) on the
+    GPU, bit for bit euclidean_distance_device + topk_rows_device.  With the four label arrays, gallery
+    items of the query's pid and camera are skipped (evaluate.py:46-48) and short rows are padded with
+    -1 / +inf.  1 <= k <= min(G, 128)."""
+    qf, gf = _as_dev_f32(qf), _as_dev_f32(gf)
+    Q, D = qf.shape
+    G = gf.shape[0]
+    labels = (q_pids, q_camids, g_pids, g_camids)
+    given = sum(a is not None for a in labels)
+    if given not in (0, 4):
+        raise _lib.ReidmiError("search: pass all four label arrays or none")
+    qp, qc, gp, gc = (_as_dev_i64(a) for a in labels) if given else (None,) * 4
+    k = int(k)
+    nb = _lib.load().reidmi_search_workspace_bytes(Q, G, D, k)
+    ws = torch.empty(max(nb, 16), device=qf.device, dtype=torch.uint8)
+    idx = torch.empty((Q, max(k, 0)), device=qf.device, dtype=torch.int32)
+    dist = torch.empty((Q, max(k, 0)), device=qf.device, dtype=torch.float32) if with_dist else None
+    _lib.call("reidmi_search_f32", _lib.ptr(qf), Q, qf.stride(0), _lib.ptr(gf), G, gf.stride(0), D, k, _lib.ptr(qp),
+              _lib.ptr(qc), _lib.ptr(gp), _lib.ptr(gc), _lib.ptr(idx), _lib.ptr(dist), max(k, 1), _lib.ptr(ws), nb,
+              _lib.stream())
+    return idx, dist
+
+
+def search(qf, gf, k, q_pids=None, q_camids=None, g_pids=None, g_camids=None, with_dist=True):
+    """search_device, returned as numpy arrays."""
+    idx, dist = search_device(qf, gf, k, q_pids, q_camids, g_pids, g_camids, with_dist)
+    return idx.cpu().numpy(), (dist.cpu().numpy() if with_dist else None)
+
+
 def eval_rows_device(dist, q_pids, g_pids, q_camids, g_camids):
     """Per-query (valid, first_match_rank, AP, n_kept) for eval_func (evaluate.py:40-80), any
     number of positives per query.  (valid = -1 / overflow = 1 were a capacity signal of older
@@ -220,6 +251,25 @@ class R1_mAP_eval():
         cmc, mAP = eval_func_device(distmat, q_pids, g_pids, q_camids, g_camids)
         self._print(cmc, mAP)
         return cmc, mAP
+
+    def rank_lists(self, k=10, remove_same_cam=True):
+        """The ranked lists behind compute()'s scores (SURVEY.md §8e "top-max_rank rank lists for
+        output"): numpy (idx int32 [num_query][k], dist fp32 [num_query][k]) of the query rows against
+        the gallery rows, features normalised as compute() does, nearest first, ties by gallery index;
+        with remove_same_cam the gallery items of the query's pid and camera are left out
+        (evaluate.py:46-48; short rows end in -1 / +inf).  Single-process semantics on this process's
+        data (no re-ranked or sharded form)."""
+        from . import distributed as rd
+        feats = torch.cat(self.feats, dim=0)
+        if self.feat_norm:
+            feats = l2_normalize_device(feats)
+        nq = self.num_query
+        lab = ()
+        if remove_same_cam:
+            lab = (np.asarray(self.pids[:nq]), np.asarray(self.camids[:nq]), np.asarray(self.pids[nq:]),
+                   np.asarray(self.camids[nq:]))
+        with rd.local():
+            return search(feats[:nq], feats[nq:], k, *lab)
 
     @staticmethod
     def _print(cmc, mAP):
