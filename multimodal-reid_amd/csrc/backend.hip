@@ -8,7 +8,7 @@
 // Bit-exact contract with oracle/reid_oracle.c: every dot product / squared norm is an
 // fmaf chain over k ascending.  The distance GEMM runs on v_mfma_f32_32x32x2_f32, whose
 // result is bit-for-bit that chain (one rounding per product, k-pairs in order).
-#include "common.h"
+#include "backend.h"
 
 #include <algorithm>
 #include <cmath>
@@ -87,24 +87,59 @@ __global__ void row_scale_kernel(const float* __restrict__ x, const float* __res
 // ------------------------------------------------------------------- distance GEMM
 // 128x128 output tile per 256-thread workgroup (2x2 waves, 64x64 per wave as 2x2
 // 32x32 MFMA tiles).  Operands staged k-major in LDS so each MFMA operand read is 32
-// consecutive floats per half-wave.
+// consecutive floats per half-wave.  The dm_* functions below are the one definition of the
+// tile (mainloops, accumulator layout, the distance value, the store) that the distance kernels
+// and the fused search (search_f32_kernel) share.
 constexpr int DM_BM = 128, DM_BN = 128, DM_BK = 16, DM_PAD = 4;
 
-template <bool COSINE>
-__global__ __launch_bounds__(256) void distmat_f32_kernel(
-    const float* __restrict__ q, const float* __restrict__ g, const float* __restrict__ qq,
-    const float* __restrict__ gg, int64_t Q, int64_t G, int64_t D, int64_t ldq, int64_t ldg,
-    float* __restrict__ out, int64_t ldo) {
-    __shared__ float sA[DM_BK][DM_BM + DM_PAD];
-    __shared__ float sB[DM_BK][DM_BN + DM_PAD];
+// A thread's place in the workgroup's tile: wave wid = 2 wm + wn owns the 64x64 quadrant (wm, wn).
+struct DmThread {
+    int tid, lane, wid, wm, wn;
+};
+__device__ __forceinline__ DmThread dm_thread() {
     const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int wm = wid >> 1, wn = wid & 1;
-    const int64_t bm = (int64_t)blockIdx.y * DM_BM, bn = (int64_t)blockIdx.x * DM_BN;
-    f32x16 acc[2][2];
+    return {tid, lane, wid, wid >> 1, wid & 1};
+}
+
+// One staged K-step of the workgroup's tile: BK / 2 K-pairs ascending, four MFMAs each.  This
+// is the only place the product is accumulated: per output the fmaf chain over k ascending.
+template <int BK, int LD>
+__device__ __forceinline__ void dm_kstep(const DmThread& t, const float (*sA)[LD], const float (*sB)[LD],
+                                         f32x16 (&acc)[2][2]) {
+    const int lane = t.lane, wm = t.wm, wn = t.wn;
+#pragma unroll
+    for (int s = 0; s < BK / 2; s++) {
+        const int kr = 2 * s + (lane >> 5);
+        const float a0 = sA[kr][wm * 64 + (lane & 31)];
+        const float a1 = sA[kr][wm * 64 + 32 + (lane & 31)];
+        const float b0 = sB[kr][wn * 64 + (lane & 31)];
+        const float b1 = sB[kr][wn * 64 + 32 + (lane & 31)];
+        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+    }
+}
+
+__device__ __forceinline__ void dm_acc_zero(f32x16 (&acc)[2][2]) {
 #pragma unroll
     for (int a = 0; a < 2; a++)
 #pragma unroll
         for (int b = 0; b < 2; b++) acc[a][b] = f32x16{};
+}
+
+// The tile functions add q[bm.., :] . g[bn.., :]^T to acc (the caller zeroes it) for the rows below
+// Q and glim (the gallery's end, or the end of a search range); rows past them count as 0.  They
+// read threadIdx.x for the staging index, not t.tid: with t.tid search_f32_kernel<true, false>
+// spills 4 B more per lane.
+// Single-stage mainloop (any D, pitch and alignment) of the search.  distmat_f32_kernel keeps its
+// own copy of the staging loop around dm_kstep: through this function it ran 1.5 - 5 % slower
+// (profiles/r08/distance_dedup_ab.txt).
+__device__ __forceinline__ void dm_tile_single(const DmThread& t, const float* q, const float* g, int64_t Q,
+                                               int64_t glim, int64_t D, int64_t ldq, int64_t ldg, int64_t bm,
+                                               int64_t bn, float (*sA)[DM_BM + DM_PAD], float (*sB)[DM_BN + DM_PAD],
+                                               f32x16 (&acc)[2][2]) {
+    const int tid = threadIdx.x;
     for (int64_t k0 = 0; k0 < D; k0 += DM_BK) {
         // stage: 128 rows x 16 k per operand, 8 elements per thread, 16 threads per row
 #pragma unroll
@@ -114,49 +149,22 @@ __global__ __launch_bounds__(256) void distmat_f32_kernel(
             int64_t gk = k0 + kk;
             int64_t qi = bm + r, gj = bn + r;
             sA[kk][r] = (qi < Q && gk < D) ? q[qi * ldq + gk] : 0.0f;
-            sB[kk][r] = (gj < G && gk < D) ? g[gj * ldg + gk] : 0.0f;
+            sB[kk][r] = (gj < glim && gk < D) ? g[gj * ldg + gk] : 0.0f;
         }
         __syncthreads();
-#pragma unroll
-        for (int s = 0; s < DM_BK / 2; s++) {
-            const int kr = 2 * s + (lane >> 5);
-            float a0 = sA[kr][wm * 64 + (lane & 31)];
-            float a1 = sA[kr][wm * 64 + 32 + (lane & 31)];
-            float b0 = sB[kr][wn * 64 + (lane & 31)];
-            float b1 = sB[kr][wn * 64 + 32 + (lane & 31)];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-        }
+        dm_kstep<DM_BK>(t, sA, sB, acc);
         __syncthreads();
     }
-#pragma unroll
-    for (int mt = 0; mt < 2; mt++)
-#pragma unroll
-        for (int nt = 0; nt < 2; nt++)
-#pragma unroll
-            for (int r = 0; r < 16; r++) {
-                int64_t i = bm + wm * 64 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                int64_t j = bn + wn * 64 + nt * 32 + (lane & 31);
-                if (i < Q && j < G) {
-                    if constexpr (COSINE) {
-                        // evaluate.py:16-26: arccos(clip(q.g * (1/(|q||g|)), -1+1e-5, 1-1e-5))
-                        const float c = acc[mt][nt][r] * (1.0f / (__builtin_sqrtf(qq[i]) * __builtin_sqrtf(gg[j])));
-                        out[i * ldo + j] = acosf(fminf(fmaxf(c, -1.0f + 1e-5f), 1.0f - 1e-5f));
-                    } else {
-                        out[i * ldo + j] = __builtin_fmaf(-2.0f, acc[mt][nt][r], qq[i] + gg[j]);
-                    }
-                }
-            }
 }
 
-// Pipelined variant (D, ldq, ldg multiples of 4, 16-byte aligned rows): K-step DM2_BK, two
+// Pipelined mainloop (D, ldq, ldg multiples of 4, 16-byte aligned rows): K-step DM2_BK, two
 // LDS stages, the next K-step's operands loaded as coalesced float4 into registers while the
 // current one is multiplied, one barrier per K-step.
 // LDS rows padded by 1 dword so the transposed scalar stores are conflict-free.  The MFMA
-// sequence per output (k pairs ascending on v_mfma_f32_32x32x2_f32) is the one above, so the
-// result is bit-identical to distmat_f32_kernel (and to the oracle's fmaf chain).
+// sequence per output is dm_kstep's, as in dm_tile_single, so the result is bit-identical to it
+// (and to the oracle's fmaf chain).  search_f32_kernel<true, *> keeps its own copy of this loop
+// (its own four MFMAs included): through this function the labelled search ran 0.1 - 0.45 %
+// slower than the copy's slowest run (profiles/r08/distance_dedup_ab.txt).
 // K-step 16 (33 KB of LDS, 112 VGPRs): four workgroups per CU; K-step 32 ran two (66 KB) and
 // was 5 % slower at MSMT17 / re-rank-chunk sizes (profiles/r02/distmat_kstep_ab.txt).  The
 // macro is an A/B hook for tools/build_variant.py.
@@ -170,44 +178,11 @@ constexpr int DM2_BK = DM2_BK_, DM2_MINWG = 4, DM2_BAND = 4, DM2_LD = DM_BM + 1;
 constexpr int DM2_F4 = DM2_BK / 4;            // float4 per operand row and K-step
 constexpr int DM2_U = DM_BM * DM2_F4 / 256;   // float4 staging slots per thread and operand
 
-template <bool COSINE, bool SYM = false>
-__global__ __launch_bounds__(256, DM2_MINWG) void distmat2_f32_kernel(
-    const float* __restrict__ q, const float* __restrict__ g, const float* __restrict__ qq,
-    const float* __restrict__ gg, int64_t Q, int64_t G, int64_t D, int64_t ldq, int64_t ldg,
-    float* __restrict__ out, int64_t ldo) {
-    __shared__ float sA[2][DM2_BK][DM2_LD];
-    __shared__ float sB[2][DM2_BK][DM2_LD];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int wm = wid >> 1, wn = wid & 1;
-    // 1-D grid, XCD-contiguous: workgroups bid, bid+8, ... share an XCD (round-robin
-    // dispatch) and get consecutive tiles, row tile fastest, so the row tiles of one gallery
-    // panel run back to back on one XCD and its panel is fetched into that L2 once.
-    const int64_t tiles_m = (Q + DM_BM - 1) / DM_BM;
-    const int64_t nwg = (int64_t)gridDim.x;
-    const int64_t bid = blockIdx.x, xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const int64_t wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
-    int64_t bm, bn;
-    if constexpr (SYM) {
-        // the self-distance of one row set (q == g): tiles (tm, tn) with tm <= tn only, column
-        // panel tn holding tiles 0..tn (tn (tn + 1) / 2 tiles before it); the epilogue also
-        // writes the mirrored tile.  Bit-for-bit symmetric: fma(a, b, c) == fma(b, a, c) in
-        // every step of the chain, and qq[i] + gg[j] == qq[j] + gg[i] (same array).
-        int64_t tn = (int64_t)((__builtin_sqrt(8.0 * (double)wg + 1.0) - 1.0) * 0.5);
-        while ((tn + 1) * (tn + 2) / 2 <= wg) tn++;
-        while (tn * (tn + 1) / 2 > wg) tn--;
-        bm = (wg - tn * (tn + 1) / 2) * DM_BM;
-        bn = tn * DM_BN;
-    } else if (DM2_BAND > 0 && tiles_m > DM2_BAND) {
-        // bands of DM2_BAND row tiles walked column-major: the tiles an XCD runs at once
-        // form a DM2_BAND x (32 / DM2_BAND) block, so their output rows are few and long
-        const int64_t per = (int64_t)DM2_BAND * ((G + DM_BN - 1) / DM_BN), band = wg / per, r = wg - band * per;
-        const int64_t rows = tiles_m - band * DM2_BAND < DM2_BAND ? tiles_m - band * DM2_BAND : DM2_BAND;
-        bm = (band * DM2_BAND + r % rows) * DM_BM;
-        bn = (r / rows) * DM_BN;
-    } else {
-        bm = (wg % tiles_m) * DM_BM;
-        bn = (wg / tiles_m) * DM_BN;
-    }
+__device__ __forceinline__ void dm_tile_pipe(const DmThread& t, const float* q, const float* g, int64_t Q,
+                                             int64_t glim, int64_t D, int64_t ldq, int64_t ldg, int64_t bm,
+                                             int64_t bn, float (*sA)[DM2_BK][DM2_LD], float (*sB)[DM2_BK][DM2_LD],
+                                             f32x16 (&acc)[2][2]) {
+    const int tid = threadIdx.x;
     // staging slots: float4 f = tid + 256u -> row f / DM2_F4, k group (f % DM2_F4) * 4
     const float* pa[DM2_U];
     const float* pb[DM2_U];
@@ -219,7 +194,7 @@ __global__ __launch_bounds__(256, DM2_MINWG) void distmat2_f32_kernel(
         srow[u] = f / DM2_F4;
         sk[u] = (f % DM2_F4) * 4;
         va[u] = bm + srow[u] < Q;
-        vb[u] = bn + srow[u] < G;
+        vb[u] = bn + srow[u] < glim;
         pa[u] = q + (va[u] ? bm + srow[u] : 0) * ldq + sk[u];
         pb[u] = g + (vb[u] ? bn + srow[u] : 0) * ldg + sk[u];
     }
@@ -245,11 +220,6 @@ __global__ __launch_bounds__(256, DM2_MINWG) void distmat2_f32_kernel(
             sB[st][sk[u] + 3][srow[u]] = rb[u].w;
         }
     };
-    f32x16 acc[2][2];
-#pragma unroll
-    for (int a = 0; a < 2; a++)
-#pragma unroll
-        for (int b = 0; b < 2; b++) acc[a][b] = f32x16{};
     gload(0);
     lstore(0);
     __syncthreads();
@@ -257,35 +227,44 @@ __global__ __launch_bounds__(256, DM2_MINWG) void distmat2_f32_kernel(
     for (int64_t kt = 0; kt < nk; kt++) {
         const int cur = (int)(kt & 1);
         if (kt + 1 < nk) gload((kt + 1) * DM2_BK);
-#pragma unroll
-        for (int s = 0; s < DM2_BK / 2; s++) {
-            const int kr = 2 * s + (lane >> 5);
-            const float a0 = sA[cur][kr][wm * 64 + (lane & 31)];
-            const float a1 = sA[cur][kr][wm * 64 + 32 + (lane & 31)];
-            const float b0 = sB[cur][kr][wn * 64 + (lane & 31)];
-            const float b1 = sB[cur][kr][wn * 64 + 32 + (lane & 31)];
-            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-        }
+        dm_kstep<DM2_BK>(t, sA[cur], sB[cur], acc);
         if (kt + 1 < nk) lstore(cur ^ 1);
         __syncthreads();
     }
+}
+
+// The accumulator layout of v_mfma_f32_32x32x2_f32: element r of acc[mt][nt] in this lane is
+// row dm_lane_row, column dm_lane_col of the workgroup's tile (wm, wn: the wave's quadrant).
+// search_f32_kernel's epilogue writes the same two expressions out (il, j): keep them in step.
+__device__ __forceinline__ int dm_lane_row(int wm, int mt, int r, int lane) {
+    return wm * 64 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
+}
+__device__ __forceinline__ int dm_lane_col(int wn, int nt, int lane) { return wn * 64 + nt * 32 + (lane & 31); }
+
+// The distance: ||q||^2 + ||g||^2 - 2 q.g with one rounding in the sum of norms and one in the fma.
+__device__ __forceinline__ float dm_value(float acc, float qq, float gg) { return __builtin_fmaf(-2.0f, acc, qq + gg); }
+
+// Store epilogue of the distance kernels.  SYM (the self-distance, q == g): also the mirrored tile.
+template <bool COSINE, bool SYM>
+__device__ __forceinline__ void dm_store_tile(const DmThread& t, const f32x16 (&acc)[2][2], const float* qq,
+                                              const float* gg, int64_t Q, int64_t G, int64_t bm, int64_t bn,
+                                              float* out, int64_t ldo) {
+    const int lane = t.lane, wm = t.wm, wn = t.wn;
 #pragma unroll
     for (int mt = 0; mt < 2; mt++)
 #pragma unroll
         for (int nt = 0; nt < 2; nt++)
 #pragma unroll
             for (int r = 0; r < 16; r++) {
-                int64_t i = bm + wm * 64 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
-                int64_t j = bn + wn * 64 + nt * 32 + (lane & 31);
+                const int64_t i = bm + dm_lane_row(wm, mt, r, lane);
+                const int64_t j = bn + dm_lane_col(wn, nt, lane);
                 if (i < Q && j < G) {
                     if constexpr (COSINE) {
+                        // evaluate.py:16-26: arccos(clip(q.g * (1/(|q||g|)), -1+1e-5, 1-1e-5))
                         const float c = acc[mt][nt][r] * (1.0f / (__builtin_sqrtf(qq[i]) * __builtin_sqrtf(gg[j])));
                         out[i * ldo + j] = acosf(fminf(fmaxf(c, -1.0f + 1e-5f), 1.0f - 1e-5f));
                     } else {
-                        const float v = __builtin_fmaf(-2.0f, acc[mt][nt][r], qq[i] + gg[j]);
+                        const float v = dm_value(acc[mt][nt][r], qq[i], gg[j]);
                         out[i * ldo + j] = v;
                         if (SYM && bm != bn) out[j * ldo + i] = v;  // the mirrored tile
                     }
@@ -293,7 +272,147 @@ __global__ __launch_bounds__(256, DM2_MINWG) void distmat2_f32_kernel(
             }
 }
 
-static bool dm2_ok(const float* q, int64_t ldq, const float* g, int64_t ldg, int64_t D);
+// 1-D grid, XCD-contiguous: workgroups bid, bid+8, ... share an XCD (round-robin dispatch) and
+// get consecutive numbers, so what consecutive numbers share is fetched into that XCD's L2 once.
+__device__ __forceinline__ int64_t xcd_contiguous_wg() {
+    const int64_t nwg = (int64_t)gridDim.x;
+    const int64_t bid = blockIdx.x, xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
+    return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+}
+
+template <bool COSINE>
+__global__ __launch_bounds__(256) void distmat_f32_kernel(
+    const float* __restrict__ q, const float* __restrict__ g, const float* __restrict__ qq,
+    const float* __restrict__ gg, int64_t Q, int64_t G, int64_t D, int64_t ldq, int64_t ldg,
+    float* __restrict__ out, int64_t ldo) {
+    __shared__ float sA[DM_BK][DM_BM + DM_PAD];
+    __shared__ float sB[DM_BK][DM_BN + DM_PAD];
+    const DmThread t = dm_thread();
+    const int64_t bm = (int64_t)blockIdx.y * DM_BM, bn = (int64_t)blockIdx.x * DM_BN;
+    f32x16 acc[2][2];
+    dm_acc_zero(acc);
+    const int tid = threadIdx.x;
+    for (int64_t k0 = 0; k0 < D; k0 += DM_BK) {
+#pragma unroll
+        for (int u = 0; u < 8; u++) {
+            int e = tid + 256 * u;
+            int r = e >> 4, kk = e & 15;
+            int64_t gk = k0 + kk;
+            int64_t qi = bm + r, gj = bn + r;
+            sA[kk][r] = (qi < Q && gk < D) ? q[qi * ldq + gk] : 0.0f;
+            sB[kk][r] = (gj < G && gk < D) ? g[gj * ldg + gk] : 0.0f;
+        }
+        __syncthreads();
+        dm_kstep<DM_BK>(t, sA, sB, acc);
+        __syncthreads();
+    }
+    dm_store_tile<COSINE, false>(t, acc, qq, gg, Q, G, bm, bn, out, ldo);
+}
+
+template <bool COSINE, bool SYM = false>
+__global__ __launch_bounds__(256, DM2_MINWG) void distmat2_f32_kernel(
+    const float* __restrict__ q, const float* __restrict__ g, const float* __restrict__ qq,
+    const float* __restrict__ gg, int64_t Q, int64_t G, int64_t D, int64_t ldq, int64_t ldg,
+    float* __restrict__ out, int64_t ldo) {
+    __shared__ float sA[2][DM2_BK][DM2_LD];
+    __shared__ float sB[2][DM2_BK][DM2_LD];
+    // consecutive tiles, row tile fastest, so the row tiles of one gallery panel run back to back
+    // on one XCD and its panel is fetched into that L2 once
+    const int64_t tiles_m = (Q + DM_BM - 1) / DM_BM;
+    const int64_t wg = xcd_contiguous_wg();
+    int64_t bm, bn;
+    if constexpr (SYM) {
+        // the self-distance of one row set (q == g): tiles (tm, tn) with tm <= tn only, column
+        // panel tn holding tiles 0..tn (tn (tn + 1) / 2 tiles before it); the epilogue also
+        // writes the mirrored tile.  Bit-for-bit symmetric: fma(a, b, c) == fma(b, a, c) in
+        // every step of the chain, and qq[i] + gg[j] == qq[j] + gg[i] (same array).
+        int64_t tn = (int64_t)((__builtin_sqrt(8.0 * (double)wg + 1.0) - 1.0) * 0.5);
+        while ((tn + 1) * (tn + 2) / 2 <= wg) tn++;
+        while (tn * (tn + 1) / 2 > wg) tn--;
+        bm = (wg - tn * (tn + 1) / 2) * DM_BM;
+        bn = tn * DM_BN;
+    } else if (DM2_BAND > 0 && tiles_m > DM2_BAND) {
+        // bands of DM2_BAND row tiles walked column-major: the tiles an XCD runs at once
+        // form a DM2_BAND x (32 / DM2_BAND) block, so their output rows are few and long
+        const int64_t per = (int64_t)DM2_BAND * ((G + DM_BN - 1) / DM_BN), band = wg / per, r = wg - band * per;
+        const int64_t rows = tiles_m - band * DM2_BAND < DM2_BAND ? tiles_m - band * DM2_BAND : DM2_BAND;
+        bm = (band * DM2_BAND + r % rows) * DM_BM;
+        bn = (r / rows) * DM_BN;
+    } else {
+        bm = (wg % tiles_m) * DM_BM;
+        bn = (wg / tiles_m) * DM_BN;
+    }
+    const DmThread t = dm_thread();
+    f32x16 acc[2][2];
+    dm_acc_zero(acc);
+    dm_tile_pipe(t, q, g, Q, G, D, ldq, ldg, bm, bn, sA, sB, acc);
+    dm_store_tile<COSINE, SYM>(t, acc, qq, gg, Q, G, bm, bn, out, ldo);
+}
+
+static bool dm2_ok(const float* q, int64_t ldq, const float* g, int64_t ldg, int64_t D) {
+    return D % 4 == 0 && ldq % 4 == 0 && ldg % 4 == 0 && ((uintptr_t)q & 15) == 0 && ((uintptr_t)g & 15) == 0;
+}
+
+// The one pick and launch of the distance kernel, norms given: the pipelined kernel when the
+// operands allow (variant 1 forces the single-stage one), for sym (q == g, Q == G) its
+// upper-triangle form.
+static int distmat_dispatch(bool cosine, bool sym, int variant, const float* q, int64_t Q, int64_t ldq, const float* g,
+                            int64_t G, int64_t ldg, int64_t D, const float* qq, const float* gg, float* out,
+                            int64_t ldo, hipStream_t s) {
+    const bool pipe = dm2_ok(q, ldq, g, ldg, D) && variant != 1;
+    auto launch = [&](auto kernel, dim3 grid) {
+        hipLaunchKernelGGL(kernel, grid, dim3(256), 0, s, q, g, qq, gg, Q, G, D, ldq, ldg, out, ldo);
+    };
+    if (sym && pipe) {
+        const int64_t T = (Q + DM_BM - 1) / DM_BM;
+        const int64_t tiles = T * (T + 1) / 2;
+        RM_REQUIRE(tiles < (1ll << 31), "distmat_self: too many tiles");
+        launch(distmat2_f32_kernel<false, true>, dim3((unsigned)tiles));
+    } else {
+        const dim3 grid(ceil_div(G, DM_BN), ceil_div(Q, DM_BM));
+        RM_REQUIRE(grid.y <= 65535, "distmat: too many query rows for one launch");
+        const dim3 grid1((unsigned)((int64_t)grid.x * grid.y));
+        if (cosine) {
+            if (pipe) launch(distmat2_f32_kernel<true>, grid1);
+            else launch(distmat_f32_kernel<true>, grid);
+        } else {
+            if (pipe) launch(distmat2_f32_kernel<false>, grid1);
+            else launch(distmat_f32_kernel<false>, grid);
+        }
+    }
+    RM_LAUNCHED();
+    return OK;
+}
+
+// ws: Q + G floats (the squared row norms).  variant: reidmi_distmat_f32_variant.
+int distmat_impl(bool cosine, const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G, int64_t ldg,
+                 int64_t D, float* out, int64_t ldo, float* ws, void* stream, int variant = 0) {
+    RM_REQUIRE(variant == 0 || variant == 1, "distmat variant: 0 auto, 1 single-stage");
+    RM_REQUIRE(Q >= 0 && G >= 0 && D > 0 && ldq >= D && ldg >= D && ldo >= G, "distmat: bad shape");
+    RM_REQUIRE(ws != nullptr, "distmat: workspace (Q+G floats) required");
+    if (Q == 0 || G == 0) return OK;
+    hipStream_t s = (hipStream_t)stream;
+    float* qq = ws;
+    float* gg = ws + Q;
+    rows_sqnorm_launch(q, Q, D, ldq, qq, s);
+    RM_LAUNCHED();
+    rows_sqnorm_launch(g, G, D, ldg, gg, s);
+    RM_LAUNCHED();
+    return distmat_dispatch(cosine, false, variant, q, Q, ldq, g, G, ldg, D, qq, gg, out, ldo, s);
+}
+
+int distmat_launch(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G, int64_t ldg, int64_t D,
+                   float* out, int64_t ldo, float* ws, hipStream_t s) {
+    return distmat_impl(false, q, Q, ldq, g, G, ldg, D, out, ldo, ws, s);
+}
+
+// Euclidean distance with precomputed squared row norms qq[Q], gg[G] (row_sqnorm_kernel).
+int distmat_pre_launch(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G, int64_t ldg, int64_t D,
+                       const float* qq, const float* gg, float* out, int64_t ldo, hipStream_t s) {
+    RM_REQUIRE(Q >= 0 && G >= 0 && D > 0 && ldq >= D && ldg >= D && ldo >= G && qq && gg, "distmat: bad shape");
+    if (Q == 0 || G == 0) return OK;
+    return distmat_dispatch(false, false, 0, q, Q, ldq, g, G, ldg, D, qq, gg, out, ldo, s);
+}
 
 // Self-distance of x [N][D] (the one-call re-rank's N x N matrix, reranking.py:36-44): the
 // upper-triangle tiles and their mirror images, half the FLOPs of distmat_launch(x, x), same
@@ -303,23 +422,7 @@ int distmat_self_launch(const float* x, int64_t N, int64_t ldx, int64_t D, float
     RM_REQUIRE(N > 0 && D > 0 && ldx >= D && ldo >= N && ws != nullptr, "distmat_self: bad shape");
     rows_sqnorm_launch(x, N, D, ldx, ws, s);
     RM_LAUNCHED();
-    if (!dm2_ok(x, ldx, x, ldx, D)) {
-        dim3 grid(ceil_div(N, DM_BN), ceil_div(N, DM_BM));
-        RM_REQUIRE(grid.y <= 65535, "distmat: too many query rows for one launch");
-        hipLaunchKernelGGL(distmat_f32_kernel<false>, grid, dim3(256), 0, s, x, x, ws, ws, N, N, D, ldx, ldx, out, ldo);
-    } else {
-        const int64_t T = (N + DM_BM - 1) / DM_BM;
-        const int64_t tiles = T * (T + 1) / 2;
-        RM_REQUIRE(tiles < (1ll << 31), "distmat_self: too many tiles");
-        hipLaunchKernelGGL((distmat2_f32_kernel<false, true>), dim3((unsigned)tiles), dim3(256), 0, s, x, x, ws, ws, N, N,
-                           D, ldx, ldx, out, ldo);
-    }
-    RM_LAUNCHED();
-    return OK;
-}
-
-static bool dm2_ok(const float* q, int64_t ldq, const float* g, int64_t ldg, int64_t D) {
-    return D % 4 == 0 && ldq % 4 == 0 && ldg % 4 == 0 && ((uintptr_t)q & 15) == 0 && ((uintptr_t)g & 15) == 0;
+    return distmat_dispatch(false, true, 0, x, N, ldx, x, N, ldx, D, ws, ws, out, ldo, s);
 }
 
 // ---------------------------------------------------------------- key helpers
@@ -453,9 +556,10 @@ __global__ __launch_bounds__(256) void topk_rows_kernel(const float* __restrict_
 // ------------------------------------------------------------- fused top-k search
 // reidmi_search_f32: the k nearest gallery rows of every query row without the Q x G matrix.
 // A workgroup owns one 128-row query band and one contiguous gallery range [c0, c1); it walks
-// the range in 128-column tiles with the distance kernels' mainloops (PIPE: distmat2_f32_kernel's,
-// else distmat_f32_kernel's; the same MFMA chain per output, so v below has the distance
-// kernel's bits) and selects in the epilogue instead of storing:
+// the range in 128-column tiles with the distance kernels' mainloops (PIPE: a copy of
+// dm_tile_pipe, else dm_tile_single, whose K-step is the distance kernels' dm_kstep) and their
+// v = dm_value, so v below has the distance kernel's bits, and selects in the epilogue instead
+// of storing:
 //   * (v, j) is kept when j passes the label predicate and key_less(v, j, thr[row]); thr[row]
 //     is the row's current K-th key in LDS (none until K candidates were seen) and only falls;
 //   * kept pairs are appended to the row's list of `cap` entries in the workspace (L2-resident:
@@ -520,14 +624,12 @@ __global__ __launch_bounds__(256, DM2_MINWG) void search_f32_kernel(
     __shared__ float s_tv[DM_BM], s_qq[DM_BM];
     __shared__ int s_ti[DM_BM], s_cnt[DM_BM];
     __shared__ int64_t s_qp[LABELS ? DM_BM : 1], s_qc[LABELS ? DM_BM : 1];
-    const int tid = threadIdx.x, lane = tid & 63, wid = tid >> 6;
-    const int wm = wid >> 1, wn = wid & 1;
-    // XCD-contiguous order (distmat2_f32_kernel), band fastest: the bands of one gallery range
-    // run side by side on one XCD and share its tiles in that L2
+    const DmThread t = dm_thread();
+    const int tid = t.tid, lane = t.lane, wid = t.wid, wm = t.wm, wn = t.wn;
+    // band fastest: the bands of one gallery range run side by side on one XCD and share its
+    // tiles in that L2
     const int64_t bands = (Q + DM_BM - 1) / DM_BM;
-    const int64_t nwg = (int64_t)gridDim.x;
-    const int64_t bid = blockIdx.x, xcd = bid & 7, q8 = nwg >> 3, r8 = nwg & 7;
-    const int64_t wg = (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
+    const int64_t wg = xcd_contiguous_wg();
     const int64_t band = wg % bands, split = wg / bands, bm = band * DM_BM;
     const int64_t c0 = split * range_len, c1 = c0 + range_len < G ? c0 + range_len : G;
     float2* const mylists = lists + (split * bands + band) * DM_BM * (int64_t)cap;
@@ -547,12 +649,10 @@ __global__ __launch_bounds__(256, DM2_MINWG) void search_f32_kernel(
     for (int64_t bn = c0;; bn += DM_BN) {
         if (bn < c1) {
             f32x16 acc[2][2];
-#pragma unroll
-            for (int a = 0; a < 2; a++)
-#pragma unroll
-                for (int b = 0; b < 2; b++) acc[a][b] = f32x16{};
+            dm_acc_zero(acc);
+            // the stages are carved out of smem (the compaction scratch between tiles); gallery rows end at c1
             if constexpr (PIPE) {
-                // distmat2_f32_kernel's mainloop; gallery rows end at c1
+                // a copy of dm_tile_pipe (see there); gallery rows end at c1
                 float(*sA)[DM2_BK][DM2_LD] = (float(*)[DM2_BK][DM2_LD])smem;
                 float(*sB)[DM2_BK][DM2_LD] = (float(*)[DM2_BK][DM2_LD])(smem + 2 * DM2_BK * DM2_LD);
                 const float* pa[DM2_U];
@@ -614,36 +714,11 @@ __global__ __launch_bounds__(256, DM2_MINWG) void search_f32_kernel(
                     __syncthreads();
                 }
             } else {
-                // distmat_f32_kernel's mainloop (any D, pitch and alignment)
-                float(*sA)[DM_BM + DM_PAD] = (float(*)[DM_BM + DM_PAD])smem;
-                float(*sB)[DM_BN + DM_PAD] = (float(*)[DM_BN + DM_PAD])(smem + DM_BK * (DM_BM + DM_PAD));
-                for (int64_t k0 = 0; k0 < D; k0 += DM_BK) {
-#pragma unroll
-                    for (int u = 0; u < 8; u++) {
-                        const int e = tid + 256 * u;
-                        const int r = e >> 4, kk = e & 15;
-                        const int64_t gk = k0 + kk;
-                        const int64_t qi = bm + r, gj = bn + r;
-                        sA[kk][r] = (qi < Q && gk < D) ? q[qi * ldq + gk] : 0.0f;
-                        sB[kk][r] = (gj < c1 && gk < D) ? g[gj * ldg + gk] : 0.0f;
-                    }
-                    __syncthreads();
-#pragma unroll
-                    for (int s = 0; s < DM_BK / 2; s++) {
-                        const int kr = 2 * s + (lane >> 5);
-                        const float a0 = sA[kr][wm * 64 + (lane & 31)];
-                        const float a1 = sA[kr][wm * 64 + 32 + (lane & 31)];
-                        const float b0 = sB[kr][wn * 64 + (lane & 31)];
-                        const float b1 = sB[kr][wn * 64 + 32 + (lane & 31)];
-                        acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
-                        acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
-                        acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
-                        acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
-                    }
-                    __syncthreads();
-                }
+                dm_tile_single(t, q, g, Q, c1, D, ldq, ldg, bm, bn, (float(*)[DM_BM + DM_PAD])smem,
+                               (float(*)[DM_BN + DM_PAD])(smem + DM_BK * (DM_BM + DM_PAD)), acc);
             }
-            // epilogue: the distance kernels' v, filtered against the row's threshold
+            // epilogue: the distance kernels' v, filtered against the row's threshold.  il and j are
+            // dm_lane_row / dm_lane_col written out: through the functions the kernel spills 8 B more per lane
 #pragma unroll
             for (int nt = 0; nt < 2; nt++) {
                 const int64_t j = bn + wn * 64 + nt * 32 + (lane & 31);
@@ -657,7 +732,7 @@ __global__ __launch_bounds__(256, DM2_MINWG) void search_f32_kernel(
                     for (int r = 0; r < 16; r++) {
                         const int il = wm * 64 + mt * 32 + (r & 3) + 8 * (r >> 2) + 4 * (lane >> 5);
                         if (bm + il >= Q) continue;
-                        const float v = __builtin_fmaf(-2.0f, acc[mt][nt][r], s_qq[il] + ggj);
+                        const float v = dm_value(acc[mt][nt][r], s_qq[il], ggj);
                         const float tv = s_tv[il];
                         if (!(v <= tv)) continue;
                         if (!key_less(v, (int)j, tv, s_ti[il])) continue;
@@ -1222,8 +1297,6 @@ __global__ __launch_bounds__(256) void rank_select_sv_kernel(const int32_t* __re
     }
     if (threadIdx.x == 0) need[r] = 1;
 }
-
-void rank_select_consts(int D, float c[3]);
 
 int rr_sample_launch(const float* hs, int64_t lds, int64_t ns, const float* sqn, const float* nrm, const float* nmax2,
                      int64_t row0, int64_t rows, int K, int D, float4* meta, float* wrow, int32_t* cnt, int cap,
@@ -2115,30 +2188,6 @@ int topk_launch(const float* x, int64_t rows, int64_t cols, int64_t ldx, const f
     return OK;
 }
 
-int distmat_impl(bool cosine, const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G, int64_t ldg,
-                 int64_t D, float* out, int64_t ldo, float* ws, void* stream, int variant = 0);
-
-int distmat_launch(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G, int64_t ldg, int64_t D,
-                   float* out, int64_t ldo, float* ws, hipStream_t s) {
-    return distmat_impl(false, q, Q, ldq, g, G, ldg, D, out, ldo, ws, s);
-}
-
-// Euclidean distance with precomputed squared row norms qq[Q], gg[G] (row_sqnorm_kernel).
-int distmat_pre_launch(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G, int64_t ldg, int64_t D,
-                       const float* qq, const float* gg, float* out, int64_t ldo, hipStream_t s) {
-    RM_REQUIRE(Q >= 0 && G >= 0 && D > 0 && ldq >= D && ldg >= D && ldo >= G && qq && gg, "distmat: bad shape");
-    if (Q == 0 || G == 0) return OK;
-    dim3 grid(ceil_div(G, DM_BN), ceil_div(Q, DM_BM));
-    RM_REQUIRE(grid.y <= 65535, "distmat: too many query rows for one launch");
-    if (dm2_ok(q, ldq, g, ldg, D))
-        hipLaunchKernelGGL(distmat2_f32_kernel<false>, dim3((unsigned)((int64_t)grid.x * grid.y)), dim3(256), 0, s, q, g,
-                           qq, gg, Q, G, D, ldq, ldg, out, ldo);
-    else
-        hipLaunchKernelGGL(distmat_f32_kernel<false>, grid, dim3(256), 0, s, q, g, qq, gg, Q, G, D, ldq, ldg, out, ldo);
-    RM_LAUNCHED();
-    return OK;
-}
-
 }  // namespace reidmi
 
 using namespace reidmi;
@@ -2159,39 +2208,6 @@ REIDMI_API int reidmi_l2norm_f32(const float* x, int64_t n, int64_t d, int64_t l
     rows_sqnorm_launch(x, n, d, ldx, ws, s);
     RM_LAUNCHED();
     hipLaunchKernelGGL(row_scale_kernel, dim3((unsigned)n), dim3(256), 0, s, x, ws, d, ldx, y, ldy);
-    RM_LAUNCHED();
-    return OK;
-}
-
-int reidmi::distmat_impl(bool cosine, const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G,
-                        int64_t ldg, int64_t D, float* out, int64_t ldo, float* ws, void* stream, int variant) {
-    RM_REQUIRE(variant == 0 || variant == 1, "distmat variant: 0 auto, 1 single-stage");
-    RM_REQUIRE(Q >= 0 && G >= 0 && D > 0 && ldq >= D && ldg >= D && ldo >= G, "distmat: bad shape");
-    RM_REQUIRE(ws != nullptr, "distmat: workspace (Q+G floats) required");
-    if (Q == 0 || G == 0) return OK;
-    hipStream_t s = (hipStream_t)stream;
-    float* qq = ws;
-    float* gg = ws + Q;
-    rows_sqnorm_launch(q, Q, D, ldq, qq, s);
-    RM_LAUNCHED();
-    rows_sqnorm_launch(g, G, D, ldg, gg, s);
-    RM_LAUNCHED();
-    dim3 grid(ceil_div(G, DM_BN), ceil_div(Q, DM_BM));
-    RM_REQUIRE(grid.y <= 65535, "distmat: too many query rows for one launch");
-    const bool v2 = dm2_ok(q, ldq, g, ldg, D) && variant != 1;
-    const dim3 grid1((unsigned)((int64_t)grid.x * grid.y));
-    if (cosine) {
-        if (v2)
-            hipLaunchKernelGGL(distmat2_f32_kernel<true>, grid1, dim3(256), 0, s, q, g, qq, gg, Q, G, D, ldq, ldg, out, ldo);
-        else
-            hipLaunchKernelGGL(distmat_f32_kernel<true>, grid, dim3(256), 0, s, q, g, qq, gg, Q, G, D, ldq, ldg, out, ldo);
-    } else {
-        if (v2)
-            hipLaunchKernelGGL(distmat2_f32_kernel<false>, grid1, dim3(256), 0, s, q, g, qq, gg, Q, G, D, ldq, ldg, out,
-                               ldo);
-        else
-            hipLaunchKernelGGL(distmat_f32_kernel<false>, grid, dim3(256), 0, s, q, g, qq, gg, Q, G, D, ldq, ldg, out, ldo);
-    }
     RM_LAUNCHED();
     return OK;
 }

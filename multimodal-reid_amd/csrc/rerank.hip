@@ -16,33 +16,11 @@
 // Arithmetic mirrors numpy exactly: float32 exp = numpy's AVX512F/AVX2 polynomial
 // (pinned against numpy 2.2.6), float32 pairwise sum, fp16 ufuncs = op in fp32 then RNE.
 #include <algorithm>
-#include "common.h"
+#include "backend.h"
 #include "gemm.h"
 
 
 namespace reidmi {
-
-int rank_select_launch(float* dot, int64_t ldd, const float* feat, int64_t ldf, int D, const float* sqn,
-                       const float* nrm, const float* nmax2, int64_t row0, int64_t rows, int64_t N, int K,
-                       int32_t* rank_out, float* rowmax_out, int32_t* need, hipStream_t s);
-void rank_select_consts(int D, float c[3]);
-int norm_max_launch(const float* sqn, const float* nrm, int64_t N, float* out2, hipStream_t s);
-int rr_sample_launch(const float* hs, int64_t lds, int64_t ns, const float* sqn, const float* nrm, const float* nmax2,
-                     int64_t row0, int64_t rows, int K, int D, float4* meta, float* wrow, int32_t* cnt, int cap,
-                     hipStream_t s);
-int rank_select_sv_launch(const int32_t* cnt, const int2* list, int cap, const float* wrow, const float* feat,
-                          int64_t ldf, int D, const float* sqn, int64_t row0, int64_t rows, int K, int32_t* rank_out,
-                          float* rowmax_out, int32_t* need, hipStream_t s);
-int feat16_launch(const float* x, int64_t N, int64_t D, int64_t ldx, void* y, int64_t Np, int64_t Dp,
-                  int32_t* range_ok, hipStream_t s);
-int topk_launch(const float* x, int64_t rows, int64_t cols, int64_t ldx, const float* row_div, int k,
-                int32_t* out_idx, float* out_val, int64_t ldo, hipStream_t s);
-int distmat_self_launch(const float* x, int64_t N, int64_t ldx, int64_t D, float* out, int64_t ldo, float* ws,
-                        hipStream_t s);
-int distmat_launch(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G, int64_t ldg, int64_t D,
-                   float* out, int64_t ldo, float* ws, hipStream_t s);
-int distmat_pre_launch(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G, int64_t ldg, int64_t D,
-                       const float* qq, const float* gg, float* out, int64_t ldo, hipStream_t s);
 
 // No capacity limits (the reference has none, reranking.py:51-78): every bound below only
 // picks the kernel.  A V row holds at most kf (kh1 + 1) entries (the k-reciprocal set plus one

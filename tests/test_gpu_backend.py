@@ -41,7 +41,7 @@ def test_distmat_bitexact(gpu, Q, G, D):
     d = _ev().euclidean_distance(torch.from_numpy(q), torch.from_numpy(g))
     assert isinstance(d, np.ndarray) and d.dtype == np.float32
     assert np.array_equal(d.view(np.uint32), ref)
-    # per-call kernel choice: the pipelined K-step-32 kernel (D % 4 == 0) and the single-stage one
+    # per-call kernel choice: the pipelined K-step-16 kernel (D % 4 == 0) and the single-stage one
     qd, gd = torch.from_numpy(q).cuda(), torch.from_numpy(g).cuda()
     for v in (0, 1):
         out = torch.empty(Q, G, device="cuda")
@@ -49,6 +49,28 @@ def test_distmat_bitexact(gpu, Q, G, D):
         _lib.call_tools("reidmi_distmat_f32_variant", _lib.ptr(qd), Q, D, _lib.ptr(gd), G, D, D, _lib.ptr(out), G,
                   _lib.ptr(ws), v, _lib.stream())
         assert np.array_equal(out.cpu().numpy().view(np.uint32), ref), v
+
+
+@pytest.mark.parametrize("Q,G,D", [(37, 259, 768), (130, 129, 1280)])
+def test_cosine_both_kernels_bit_equal(gpu, Q, G, D):
+    """reidmi_cosine_f32 gives the same bits from the pipelined kernel (contiguous rows) and from
+    the single-stage kernel (the same values in rows of D + 3 floats, NaN in the padding)."""
+    from multimodal_reid_amd import _lib
+    r = np.random.default_rng(Q * 13 + G)
+    qv = torch.from_numpy(r.standard_normal((Q, D)).astype(np.float32)).cuda()
+    gv = torch.from_numpy(r.standard_normal((G, D)).astype(np.float32)).cuda()
+    outs = []
+    for pad in (0, 3):
+        q = torch.full((Q, D + pad), float("nan"), device="cuda")
+        g = torch.full((G, D + pad), float("nan"), device="cuda")
+        q[:, :D], g[:, :D] = qv, gv
+        out = torch.empty(Q, G, device="cuda")
+        ws = torch.empty(Q + G, device="cuda")
+        _lib.call("reidmi_cosine_f32", _lib.ptr(q), Q, D + pad, _lib.ptr(g), G, D + pad, D, _lib.ptr(out), G,
+                  _lib.ptr(ws), _lib.stream())
+        outs.append(out.cpu().numpy().view(np.uint32))
+    assert np.isfinite(outs[0].view(np.float32)).all()
+    assert np.array_equal(outs[0], outs[1])
 
 
 @pytest.mark.parametrize("Q,G,D", [(100, 500, 1280), (37, 259, 768), (1, 1, 2), (130, 129, 1792), (5, 300, 513),
