@@ -43,12 +43,13 @@ constexpr int JCH = RR_JCH;   // gallery columns per Jaccard workgroup (fp16 acc
 // for bounds from rr_caps; a caller passing smaller scratch gets this instead of a fault)
 enum RrFlag : int { RR_SCRATCH = 8 };
 
-static int pow2_ceil64(int64_t n) {
+// smallest power of two >= max(n, 2): the padded length of a bitonic sort of n keys
+__host__ __device__ inline int pow2_ceil(int64_t n) {
     int64_t p = 2;
     while (p < n) p <<= 1;
     return (int)p;
 }
-static int64_t al16(int64_t v) { return (v + 15) & ~(int64_t)15; }
+static int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) & ~(a - 1); }
 
 // kf = min(k1 + 1, N), kh1 = min(round(k1 / 2) + 1, N): the two depths of reranking.py:53,60
 static void kr_depths(int k1, int64_t N, int& kf, int& kh1) {
@@ -86,13 +87,13 @@ static KrSlab kr_slab(int kf, int kh1) {
     KrSlab s{};
     const int64_t nb = (int64_t)kf * (kh1 + 1);
     int64_t o = 0;
-    s.kr = o; o = al16(o + (int64_t)kf * 4);
-    s.krs = o; o = al16(o + (int64_t)pow2_ceil64(kf) * 4);
-    s.ncnt = o; o = al16(o + (int64_t)kf * 4);
-    s.acc = o; o = al16(o + (int64_t)kf * 4);
-    s.cs = o; o = al16(o + (int64_t)kf * kh1 * 4);
-    s.lst = o; o = al16(o + (int64_t)pow2_ceil64(nb) * 4);
-    s.w = o; o = al16(o + nb * 4);
+    s.kr = o; o = align_up(o + (int64_t)kf * 4, 16);
+    s.krs = o; o = align_up(o + (int64_t)pow2_ceil(kf) * 4, 16);
+    s.ncnt = o; o = align_up(o + (int64_t)kf * 4, 16);
+    s.acc = o; o = align_up(o + (int64_t)kf * 4, 16);
+    s.cs = o; o = align_up(o + (int64_t)kf * kh1 * 4, 16);
+    s.lst = o; o = align_up(o + (int64_t)pow2_ceil(nb) * 4, 16);
+    s.w = o; o = align_up(o + nb * 4, 16);
     s.bytes = o;
     return s;
 }
@@ -102,13 +103,13 @@ struct QeSlab {
 };
 static QeSlab qe_slab(int k2e, int64_t tcap) {
     QeSlab s{};
-    const int64_t P = pow2_ceil64(tcap);
+    const int64_t P = pow2_ceil(tcap);
     int64_t o = 0;
-    s.soff = o; o = al16(o + (int64_t)(k2e + 1) * 4);
-    s.scol = o; o = al16(o + tcap * 4);
-    s.sval = o; o = al16(o + tcap * 2);
-    s.okey = o; o = al16(o + P * 4);
-    s.oval = o; o = al16(o + P * 2);
+    s.soff = o; o = align_up(o + (int64_t)(k2e + 1) * 4, 16);
+    s.scol = o; o = align_up(o + tcap * 4, 16);
+    s.sval = o; o = align_up(o + tcap * 2, 16);
+    s.okey = o; o = align_up(o + P * 4, 16);
+    s.oval = o; o = align_up(o + P * 2, 16);
     s.bytes = o;
     return s;
 }
@@ -175,6 +176,38 @@ __device__ float pairwise_f32(const float* a, int n) {
     return ret;
 }
 
+// The sorting network of every stage: the workgroup sorts k[0..n) ascending (keys below
+// 0x7fffffff) and, with PAYLOAD, moves v[t] along with k[t].  k and v hold pow2_ceil(n)
+// entries; the tail is padded here.  One barrier per pass, the first one after the padding, so
+// the caller's own writes of k[0..n) need none of their own.  Every thread of the workgroup
+// calls it.  Inlined, so that a caller's LDS arrays stay LDS accesses.
+template <bool PAYLOAD>
+__device__ __forceinline__ void bitonic_sort(int32_t* k, uint16_t* v, int n) {
+    const int P = pow2_ceil(n);
+    for (int t = n + threadIdx.x; t < P; t += blockDim.x) k[t] = 0x7fffffff;
+    __syncthreads();
+    for (int kk = 2; kk <= P; kk <<= 1)
+        for (int j = kk >> 1; j > 0; j >>= 1) {
+            for (int t = threadIdx.x; t < P; t += blockDim.x) {
+                const int o = t ^ j;
+                if (o > t) {
+                    const bool up = (t & kk) == 0;
+                    const int32_t x = k[t], y = k[o];
+                    if ((x > y) == up) {
+                        k[t] = y;
+                        k[o] = x;
+                        if (PAYLOAD) {
+                            const uint16_t a = v[t];
+                            v[t] = v[o];
+                            v[o] = a;
+                        }
+                    }
+                }
+            }
+            __syncthreads();
+        }
+}
+
 // ------------------------------------------------------------------ row views
 // A set of sparse rows: CSR (off != nullptr: row r = [off[r], off[r+1])) or fixed-capacity
 // ELL (off == nullptr: row r = [r*cap, r*cap + nnz[r])).  Columns ascending in every row.
@@ -187,6 +220,12 @@ struct Rows {
     __device__ __forceinline__ int64_t beg(int64_t r) const { return off ? off[r] : r * cap; }
     __device__ __forceinline__ int len(int64_t r) const { return (int)(off ? off[r + 1] - off[r] : nnz[r]); }
 };
+static Rows csr_rows(const int64_t* off, const int32_t* col, const uint16_t* val) {
+    return Rows{off, nullptr, 0, col, val};
+}
+static Rows ell_rows(const int32_t* nnz, int64_t cap, const int32_t* col, const uint16_t* val) {
+    return Rows{nullptr, nnz, cap, col, val};
+}
 
 // Where original_dist entries come from: a materialised matrix (od != nullptr: entry
 // (i, c) = od[(i - row0) * ld + c]) or recomputed from the features with the distance
@@ -263,27 +302,6 @@ __device__ __forceinline__ bool row_has(const int32_t* R, int64_t ldr, int32_t r
     return false;
 }
 
-__device__ void bitonic_sort_i32(int32_t* a, int P) {
-    for (int k = 2; k <= P; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = threadIdx.x; t < P; t += blockDim.x) {
-                const int o = t ^ j;
-                if (o > t) {
-                    const bool up = (t & k) == 0;
-                    const int32_t x = a[t], y = a[o];
-                    if ((x > y) == up) { a[t] = y; a[o] = x; }
-                }
-            }
-            __syncthreads();
-        }
-}
-
-__device__ __forceinline__ int pow2_ceil_i(int n) {
-    int p = 1;
-    while (p < n) p <<= 1;
-    return p;
-}
-
 // v in R[row][0, kk): every load issued before any compare (no early exit: the loads of a
 // scan are independent, so they share one memory round trip per unrolled group)
 __device__ __forceinline__ bool row_has_all(const int32_t* R, int64_t ldr, int32_t row, int kk, int32_t v) {
@@ -292,6 +310,57 @@ __device__ __forceinline__ bool row_has_all(const int32_t* R, int64_t ldr, int32
 #pragma unroll 16
     for (int b = 0; b < kk; b++) hit |= p[b] == v;
     return hit;
+}
+
+// The end of a V row, from the expansion list lst[0..n) of item i to output row b
+// (reranking.py:66-71): np.unique, w = exp(-od[i, lst]), V[i, lst] = w / sum(w) in fp16.
+// lst holds pow2_ceil(n) ints and w n floats (LDS or the slab; inlined for either); wsum is
+// 4 ints of LDS.  Reached by all 256 threads; the row is complete when it returns.
+__device__ __forceinline__ void kr_finish_row(const DistSrc& ds, float dv, int64_t i, int64_t b, int32_t* lst, float* w,
+                                              int n, int* wsum, int32_t* __restrict__ vcol,
+                                              uint16_t* __restrict__ vval, int32_t* __restrict__ vnnz, int64_t vcap,
+                                              int32_t* __restrict__ flags) {
+    __shared__ int s_nu;
+    __shared__ float s_sum;
+    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    bitonic_sort<false>(lst, nullptr, n);
+    // np.unique: thread t owns a contiguous segment, counts its first occurrences, and writes
+    // them at the exclusive prefix of the counts (into w's storage, then back)
+    const int seg = (n + 255) >> 8, s0 = tid * seg, s1 = s0 + seg < n ? s0 + seg : n;
+    int cnt = 0;
+    for (int t = s0; t < s1; t++) cnt += (t == 0 || lst[t] != lst[t - 1]);
+    int incl = cnt;
+#pragma unroll
+    for (int o = 1; o < 64; o <<= 1) {
+        const int u = __shfl_up(incl, o, 64);
+        if (lane >= o) incl += u;
+    }
+    if (lane == 63) wsum[wv] = incl;
+    __syncthreads();
+    int pos = incl - cnt;
+    for (int q = 0; q < wv; q++) pos += wsum[q];
+    int32_t* u = (int32_t*)w;
+    for (int t = s0; t < s1; t++)
+        if (t == 0 || lst[t] != lst[t - 1]) u[pos++] = lst[t];
+    if (tid == 255) s_nu = pos;  // (the last segment ends the list)
+    __syncthreads();
+    const int nu = s_nu;
+    for (int t = tid; t < nu; t += blockDim.x) lst[t] = u[t];
+    __syncthreads();
+    for (int t = tid; t < nu; t += blockDim.x) w[t] = np_expf(-(dist_at(ds, i, lst[t]) / dv));
+    __syncthreads();
+    if (tid == 0) s_sum = pairwise_f32(w, nu);
+    __syncthreads();
+    if (nu > vcap) {  // cannot happen: nu <= kf (kh1 + 1) = the width rr_caps gives
+        if (tid == 0) { atomicOr(flags, RR_SCRATCH); vnnz[b] = 0; }
+        return;
+    }
+    const float sum = s_sum;
+    for (int t = tid; t < nu; t += blockDim.x) {
+        vcol[b * vcap + t] = lst[t];
+        vval[b * vcap + t] = f2h_bits(w[t] / sum);
+    }
+    if (tid == 0) vnnz[b] = nu;
 }
 
 // One 256-thread workgroup per row i = row0 + blockIdx.x of od (output row blockIdx.x).
@@ -310,11 +379,10 @@ __global__ __launch_bounds__(256) void kreciprocal_kernel(DistSrc ds, const floa
     __shared__ int32_t lst[KR_LST];
     __shared__ float w[KR_LST];
     __shared__ int wsum[4];
-    __shared__ int s_nk, s_n, s_nu;
-    __shared__ float s_sum;
+    __shared__ int s_nk, s_n;
     const int64_t b = blockIdx.x;
     const int64_t i = row0 + b;
-    const int tid = threadIdx.x, lane = tid & 63, wv = tid >> 6;
+    const int tid = threadIdx.x;
     // k-reciprocal set of i at depth k1 (reranking.py:53-56), kept in forward order
     if (tid < 64) {
         const int f = tid;
@@ -361,52 +429,7 @@ __global__ __launch_bounds__(256) void kreciprocal_kernel(DistSrc ds, const floa
         }
     }
     __syncthreads();
-    const int n = s_n;
-    const int P = pow2_ceil_i(n < 2 ? 2 : n);
-    for (int t = n + tid; t < P; t += blockDim.x) lst[t] = 0x7fffffff;
-    __syncthreads();
-    bitonic_sort_i32(lst, P);
-    // unique (np.unique): thread t owns a contiguous segment, counts its first occurrences,
-    // and writes them at the exclusive prefix of the counts (into w's storage, then back)
-    {
-        const int seg = (n + 255) >> 8, s0 = tid * seg, s1 = s0 + seg < n ? s0 + seg : n;
-        int cnt = 0;
-        for (int t = s0; t < s1; t++) cnt += (t == 0 || lst[t] != lst[t - 1]);
-        int incl = cnt;
-#pragma unroll
-        for (int o = 1; o < 64; o <<= 1) {
-            const int u = __shfl_up(incl, o, 64);
-            if (lane >= o) incl += u;
-        }
-        if (lane == 63) wsum[wv] = incl;
-        __syncthreads();
-        int pos = incl - cnt;
-        for (int q = 0; q < wv; q++) pos += wsum[q];
-        int32_t* u = (int32_t*)w;
-        for (int t = s0; t < s1; t++)
-            if (t == 0 || lst[t] != lst[t - 1]) u[pos++] = lst[t];
-        if (tid == 255) s_nu = pos;  // (the last segment ends the list)
-        __syncthreads();
-        const int nu0 = s_nu;
-        for (int t = tid; t < nu0; t += blockDim.x) lst[t] = u[t];
-        __syncthreads();
-    }
-    const int nu = s_nu;
-    const float dv = rowdiv[i];
-    for (int t = tid; t < nu; t += blockDim.x) w[t] = np_expf(-(dist_at(ds, i, lst[t]) / dv));
-    __syncthreads();
-    if (tid == 0) s_sum = pairwise_f32(w, nu);
-    __syncthreads();
-    if (nu > vcap) {  // cannot happen: nu <= kf (kh1 + 1) = the width rr_caps gives
-        if (tid == 0) { atomicOr(flags, RR_SCRATCH); vnnz[b] = 0; }
-        return;
-    }
-    const float sum = s_sum;
-    for (int t = tid; t < nu; t += blockDim.x) {
-        vcol[b * vcap + t] = lst[t];
-        vval[b * vcap + t] = f2h_bits(w[t] / sum);
-    }
-    if (tid == 0) vnnz[b] = nu;
+    kr_finish_row(ds, rowdiv[i], i, b, lst, w, s_n, wsum, vcol, vval, vnnz, vcap, flags);
 }
 
 // R3 for any k1: the same steps as kreciprocal_kernel with the lists on a per-workgroup slab
@@ -421,8 +444,7 @@ __global__ __launch_bounds__(256) void kreciprocal_generic_kernel(DistSrc ds, co
                                                                   int32_t* __restrict__ vnnz, int64_t vcap,
                                                                   int32_t* __restrict__ flags) {
     __shared__ int wsum[4];
-    __shared__ int s_nk, s_n, s_nu;
-    __shared__ float s_sum;
+    __shared__ int s_nk, s_n;
     char* base = slab + (int64_t)blockIdx.x * sl.bytes;
     int32_t* kr = (int32_t*)(base + sl.kr);
     int32_t* krs = (int32_t*)(base + sl.krs);
@@ -457,10 +479,8 @@ __global__ __launch_bounds__(256) void kreciprocal_generic_kernel(DistSrc ds, co
         }
         const int nk = s_nk;
         // a sorted copy for the intersection counts (np.intersect1d of unique sets)
-        const int Pk = pow2_ceil_i(nk < 2 ? 2 : nk);
-        for (int t = tid; t < Pk; t += blockDim.x) krs[t] = t < nk ? kr[t] : 0x7fffffff;
-        __syncthreads();
-        bitonic_sort_i32(krs, Pk);
+        for (int t = tid; t < nk; t += blockDim.x) krs[t] = kr[t];
+        bitonic_sort<false>(krs, nullptr, nk);
         // each candidate's half-depth reciprocal set and the 2/3 overlap rule (reranking.py:57-65)
         for (int t = tid; t < nk; t += blockDim.x) {
             const int32_t a = kr[t];
@@ -492,44 +512,75 @@ __global__ __launch_bounds__(256) void kreciprocal_generic_kernel(DistSrc ds, co
                 for (int q = 0; q < nc; q++) lst[bs + q] = cs[(int64_t)t * kh1 + q];
             }
         __syncthreads();
-        const int n = s_n;
-        const int P = pow2_ceil_i(n < 2 ? 2 : n);
-        for (int t = n + tid; t < P; t += blockDim.x) lst[t] = 0x7fffffff;
-        __syncthreads();
-        bitonic_sort_i32(lst, P);
-        if (tid == 0) {  // np.unique
-            int nu = 0;
-            for (int t = 0; t < n; t++)
-                if (nu == 0 || lst[t] != lst[nu - 1]) lst[nu++] = lst[t];
-            s_nu = nu;
-        }
-        __syncthreads();
-        const int nu = s_nu;
-        const float dv = rowdiv[i];
-        for (int t = tid; t < nu; t += blockDim.x) w[t] = np_expf(-(dist_at(ds, i, lst[t]) / dv));
-        __syncthreads();
-        if (tid == 0) s_sum = pairwise_f32(w, nu);
-        __syncthreads();
-        if (nu > vcap) {
-            if (tid == 0) { atomicOr(flags, RR_SCRATCH); vnnz[b] = 0; }
-        } else {
-            const float sum = s_sum;
-            for (int t = tid; t < nu; t += blockDim.x) {
-                vcol[b * vcap + t] = lst[t];
-                vval[b * vcap + t] = f2h_bits(w[t] / sum);
-            }
-            if (tid == 0) vnnz[b] = nu;
-        }
+        kr_finish_row(ds, rowdiv[i], i, b, lst, w, s_n, wsum, vcol, vval, vnnz, vcap, flags);
         __syncthreads();  // the slab and the shared counters are reused by the next row
     }
 }
 
 // --------------------------------------------------------------------- R4: QE
-// V_qe[i] = fp16( (sum_{j<k2, in order} fp32(V[R[i][j]])) / k2 ) over the union of columns,
-// i = row0 + blockIdx.x (output row blockIdx.x).  Entries of the k2 (column-sorted) rows
-// are staged in LDS; the first occurrence of each column owns it and sums that column over
-// all k2 rows in j order (binary search).
-// A row whose k2 rows stage more than LCAP entries, or that produces more than QCAP, is appended
+// V_qe[i] = fp16( (sum_{j<k2, in order} fp32(V[R[i][j]])) / k2 ) over the union of columns.
+// Both kernels stage the k2 (column-sorted) rows back to back (row j at soff[j], soff[k2]
+// entries in all), let the first occurrence of each column own it, and sort the owners'
+// (column, bits) pairs by column.  The arrays are LDS in qe_kernel and a slab in
+// qe_generic_kernel; the two steps below are inlined for either.
+
+// Copies the k2 rows to scol / sval at soff[]; row_beg(j) = where row j starts in V.  Ends with
+// a barrier.
+template <typename RowBeg>
+__device__ __forceinline__ void qe_stage_rows(const Rows& V, int k2, const int32_t* soff, int32_t* scol,
+                                              uint16_t* sval, RowBeg row_beg) {
+    for (int j = 0; j < k2; j++) {
+        const int64_t rb = row_beg(j);
+        const int n = soff[j + 1] - soff[j];
+        for (int t = threadIdx.x; t < n; t += blockDim.x) {
+            scol[soff[j] + t] = V.col[rb + t];
+            sval[soff[j] + t] = V.val[rb + t];
+        }
+    }
+    __syncthreads();
+}
+
+// Staged entry e of row j looks its column c up in the k2 rows in j order (binary search): if
+// a row before j holds c, that one owns it; otherwise e sums c over the rows, divides by k2,
+// rounds to fp16 and, unless that is zero, appends (c, bits) to ocol / oval while there are
+// fewer than cap.  *s_no (LDS) is 0 on entry.  Returns the entry count, which runs on past cap
+// (the caller's sign of an overflow).  Ends with a barrier.
+__device__ __forceinline__ int qe_owner_sums(int k2, const int32_t* soff, const int32_t* scol, const uint16_t* sval,
+                                             int32_t* ocol, uint16_t* oval, int cap, int* s_no) {
+    const int tot = soff[k2];
+    const float fk2 = (float)k2;
+    for (int e = threadIdx.x; e < tot; e += blockDim.x) {
+        int j = 0, hj = k2;  // the row of entry e: the largest j with soff[j] <= e
+        while (j < hj) {
+            const int mid = (j + hj + 1) >> 1;
+            if (soff[mid] <= e) j = mid; else hj = mid - 1;
+        }
+        const int32_t c = scol[e];
+        bool first = true;
+        float acc = 0.f;
+        for (int jj = 0; jj < k2; jj++) {
+            int lo = soff[jj], hi = soff[jj + 1];
+            while (lo < hi) {
+                const int mid = (lo + hi) >> 1;
+                if (scol[mid] < c) lo = mid + 1; else hi = mid;
+            }
+            const bool hit = lo < soff[jj + 1] && scol[lo] == c;
+            if (hit && jj < j) { first = false; break; }
+            if (hit) acc += h2f_bits(sval[lo]);
+        }
+        if (!first) continue;
+        const uint16_t h = f2h_bits(acc / fk2);
+        if (h & 0x7fff) {
+            const int p = atomicAdd(s_no, 1);
+            if (p < cap) { ocol[p] = c; oval[p] = h; }
+        }
+    }
+    __syncthreads();
+    return *s_no;
+}
+
+// Row i = row0 + blockIdx.x (output row blockIdx.x), k2 <= QE_FAST_K2, everything in LDS.  A
+// row whose k2 rows stage more than LCAP entries, or that produces more than QCAP, is appended
 // to the deferred list (dlist[atomicAdd(dcount)] = b, qnnz[b] = 0) for qe_generic_kernel.
 __global__ __launch_bounds__(256) void qe_kernel(const int32_t* __restrict__ R, int64_t ldr, int k2, int64_t row0,
                                                  Rows V, int32_t* __restrict__ qcol, uint16_t* __restrict__ qval,
@@ -568,102 +619,24 @@ __global__ __launch_bounds__(256) void qe_kernel(const int32_t* __restrict__ R, 
         if (tid == 0) { qnnz[b] = 0; dlist[atomicAdd(dcount, 1)] = (int32_t)b; }
         return;
     }
-    for (int j = 0; j < k2; j++) {
-        const int64_t rb = s_rb[j];
-        const int n = soff[j + 1] - soff[j];
-        for (int t = tid; t < n; t += blockDim.x) {
-            scol[soff[j] + t] = V.col[rb + t];
-            sval[soff[j] + t] = V.val[rb + t];
-        }
-    }
-    __syncthreads();
-    const int tot = soff[k2];
-    const float fk2 = (float)k2;
-    for (int e = tid; e < tot; e += blockDim.x) {
-        int j = 0;
-        while (soff[j + 1] <= e) j++;
-        const int32_t c = scol[e];
-        bool first = true;
-        float acc = 0.f;
-        for (int jj = 0; jj < k2; jj++) {
-            int lo = soff[jj], hi = soff[jj + 1];
-            while (lo < hi) {
-                const int mid = (lo + hi) >> 1;
-                if (scol[mid] < c) lo = mid + 1; else hi = mid;
-            }
-            const bool hit = lo < soff[jj + 1] && scol[lo] == c;
-            if (hit && jj < j) { first = false; break; }
-            if (hit) acc += h2f_bits(sval[lo]);
-        }
-        if (!first) continue;
-        const uint16_t h = f2h_bits(acc / fk2);
-        if (h & 0x7fff) {
-            const int p = atomicAdd(&s_no, 1);
-            if (p < QCAP) { ocol[p] = c; oval[p] = h; }
-        }
-    }
-    __syncthreads();
-    const int no = s_no;
+    qe_stage_rows(V, k2, soff, scol, sval, [&](int j) { return s_rb[j]; });
+    const int no = qe_owner_sums(k2, soff, scol, sval, ocol, oval, QCAP, &s_no);
     if (no > QCAP) {
         if (tid == 0) { qnnz[b] = 0; dlist[atomicAdd(dcount, 1)] = (int32_t)b; }
         return;
     }
-    // sort (column, bits) pairs by column: reuse the int sort on packed keys
-    const int P = pow2_ceil_i(no < 2 ? 2 : no);
-    int32_t* keys = scol;  // staged rows no longer needed; LCAP >= QCAP
-    __syncthreads();
-    for (int t = tid; t < P; t += blockDim.x) keys[t] = t < no ? t : 0x7fffffff;
-    __syncthreads();
-    // sort indices by ocol (columns are unique): bitonic on (ocol[idx])
-    for (int k = 2; k <= P; k <<= 1)
-        for (int jst = k >> 1; jst > 0; jst >>= 1) {
-            for (int t = tid; t < P; t += blockDim.x) {
-                const int o = t ^ jst;
-                if (o > t) {
-                    const bool up = (t & k) == 0;
-                    const int32_t x = keys[t], y = keys[o];
-                    const int32_t cx = x == 0x7fffffff ? 0x7fffffff : ocol[x];
-                    const int32_t cy = y == 0x7fffffff ? 0x7fffffff : ocol[y];
-                    if ((cx > cy) == up) { keys[t] = y; keys[o] = x; }
-                }
-            }
-            __syncthreads();
-        }
+    bitonic_sort<true>(ocol, oval, no);
     for (int t = tid; t < no; t += blockDim.x) {
-        const int32_t k = keys[t];
-        qcol[b * qcap + t] = ocol[k];
-        qval[b * qcap + t] = oval[k];
+        qcol[b * qcap + t] = ocol[t];
+        qval[b * qcap + t] = oval[t];
     }
     if (tid == 0) qnnz[b] = no;
 }
 
-// Every row(s) of i = row0 + b to all deferred rows b = dlist[d], d < *dcount (or all rows b <
-// nrows when dlist is null): the same arithmetic as qe_kernel (first occurrence of a column owns
-// it and sums it over the k2 rows in j order) with the k2 rows staged on a per-workgroup slab
-// (QeSlab, sized for k2 rows of the V bound) and the output sorted there.  mode 0: qnnz[b] = the
-// row's entry count only; mode 1: the row to CSR at qoff[b] (qnnz untouched); mode 2: the row
-// to ELL row b (width qcap) and qnnz[b].
-__device__ void bitonic_sort_i32_u16(int32_t* k, uint16_t* v, int P) {
-    for (int kk = 2; kk <= P; kk <<= 1)
-        for (int j = kk >> 1; j > 0; j >>= 1) {
-            for (int t = threadIdx.x; t < P; t += blockDim.x) {
-                const int o = t ^ j;
-                if (o > t) {
-                    const bool up = (t & kk) == 0;
-                    const int32_t x = k[t], y = k[o];
-                    if ((x > y) == up) {
-                        k[t] = y;
-                        k[o] = x;
-                        const uint16_t a = v[t];
-                        v[t] = v[o];
-                        v[o] = a;
-                    }
-                }
-            }
-            __syncthreads();
-        }
-}
-
+// The same for the rows i = row0 + b of all deferred rows b = dlist[d], d < *dcount (or all rows
+// b < nrows when dlist is null), any k2, on a per-workgroup slab (QeSlab, sized for k2 rows of the
+// V bound).  mode 0: qnnz[b] = the row's entry count only; mode 1: the row to CSR at qoff[b] (qnnz
+// untouched); mode 2: the row to ELL row b (width qcap) and qnnz[b].
 __global__ __launch_bounds__(256) void qe_generic_kernel(const int32_t* __restrict__ R, int64_t ldr, int k2,
                                                          int64_t row0, Rows V, const int32_t* __restrict__ dlist,
                                                          const int32_t* __restrict__ dcount, int64_t nrows, int mode,
@@ -681,7 +654,6 @@ __global__ __launch_bounds__(256) void qe_generic_kernel(const int32_t* __restri
     uint16_t* oval = (uint16_t*)(base + sl.oval);
     const int tid = threadIdx.x;
     const int64_t nd = dcount ? (int64_t)*dcount : nrows;
-    const float fk2 = (float)k2;
     for (int64_t d = blockIdx.x; d < nd; d += gridDim.x) {
         const int64_t b = dlist ? dlist[d] : d;
         const int64_t i = row0 + b;
@@ -696,8 +668,7 @@ __global__ __launch_bounds__(256) void qe_generic_kernel(const int32_t* __restri
             s_no = 0;
         }
         __syncthreads();
-        const int tot = s_tot;
-        if (tot < 0) {  // beyond the slab (not for tcap from rr_caps)
+        if (s_tot < 0) {  // beyond the slab (not for tcap from rr_caps)
             if (tid == 0) {
                 atomicOr(flags, RR_SCRATCH);
                 if (mode != 1) qnnz[b] = 0;
@@ -705,62 +676,15 @@ __global__ __launch_bounds__(256) void qe_generic_kernel(const int32_t* __restri
             __syncthreads();
             continue;
         }
-        for (int j = 0; j < k2; j++) {
-            const int64_t rb = V.beg(R[i * ldr + j]);
-            const int n = soff[j + 1] - soff[j];
-            for (int t = tid; t < n; t += blockDim.x) {
-                scol[soff[j] + t] = V.col[rb + t];
-                sval[soff[j] + t] = V.val[rb + t];
-            }
-        }
-        __syncthreads();
-        for (int e = tid; e < tot; e += blockDim.x) {
-            int lo = 0, hi = k2;  // the row of entry e: the largest j with soff[j] <= e
-            while (lo < hi) {
-                const int mid = (lo + hi + 1) >> 1;
-                if (soff[mid] <= e) lo = mid; else hi = mid - 1;
-            }
-            const int j = lo;
-            const int32_t c = scol[e];
-            bool first = true;
-            float acc = 0.f;
-            for (int jj = 0; jj < k2; jj++) {
-                int a = soff[jj], z = soff[jj + 1];
-                while (a < z) {
-                    const int mid = (a + z) >> 1;
-                    if (scol[mid] < c) a = mid + 1; else z = mid;
-                }
-                const bool hit = a < soff[jj + 1] && scol[a] == c;
-                if (hit && jj < j) { first = false; break; }
-                if (hit) acc += h2f_bits(sval[a]);
-            }
-            if (!first) continue;
-            const uint16_t h = f2h_bits(acc / fk2);
-            if (h & 0x7fff) {
-                const int p = atomicAdd(&s_no, 1);
-                okey[p] = c;
-                oval[p] = h;
-            }
-        }
-        __syncthreads();
-        const int no = s_no;
-        if (mode == 0) {
-            if (tid == 0) qnnz[b] = no;
-            __syncthreads();
-            continue;
-        }
-        const int P = pow2_ceil_i(no < 2 ? 2 : no);
-        for (int t = no + tid; t < P; t += blockDim.x) { okey[t] = 0x7fffffff; oval[t] = 0; }
-        __syncthreads();
-        bitonic_sort_i32_u16(okey, oval, P);
-        if (mode == 1) {
-            const int64_t o = qoff[b];
+        qe_stage_rows(V, k2, soff, scol, sval, [&](int j) { return V.beg(R[i * ldr + j]); });
+        const int no = qe_owner_sums(k2, soff, scol, sval, okey, oval, 0x7fffffff, &s_no);
+        if (mode != 0) {
+            bitonic_sort<true>(okey, oval, no);
+            const int64_t o = mode == 1 ? qoff[b] : b * qcap;
             for (int t = tid; t < no; t += blockDim.x) { qcol[o + t] = okey[t]; qval[o + t] = oval[t]; }
-        } else {
-            for (int t = tid; t < no; t += blockDim.x) { qcol[b * qcap + t] = okey[t]; qval[b * qcap + t] = oval[t]; }
-            if (tid == 0) qnnz[b] = no;
         }
-        __syncthreads();
+        if (mode != 1 && tid == 0) qnnz[b] = no;
+        __syncthreads();  // the slab and the shared counters are reused by the next row
     }
 }
 
@@ -843,37 +767,33 @@ __global__ __launch_bounds__(256) void csc_sort_kernel(const int64_t* __restrict
     const int64_t b = off[c];
     const int n = (int)(off[c + 1] - b);
     if (n < 2) return;
-    int P = 1;
-    while (P < n) P <<= 1;
-    const bool in_lds = P <= CSC_LDS;
+    const bool in_lds = pow2_ceil(n) <= CSC_LDS;
     int32_t* K = in_lds ? lk : sk + 2 * b;
     uint16_t* V = in_lds ? lv : sv + 2 * b;
-    for (int t = threadIdx.x; t < P; t += blockDim.x) {
-        K[t] = t < n ? irow[b + t] : 0x7fffffff;
-        V[t] = t < n ? ival[b + t] : 0;
+    for (int t = threadIdx.x; t < n; t += blockDim.x) {
+        K[t] = irow[b + t];
+        V[t] = ival[b + t];
     }
-    __syncthreads();
-    for (int k = 2; k <= P; k <<= 1)
-        for (int j = k >> 1; j > 0; j >>= 1) {
-            for (int t = threadIdx.x; t < P; t += blockDim.x) {
-                const int o = t ^ j;
-                if (o > t) {
-                    const int32_t a = K[t], d = K[o];
-                    if ((d < a) == ((t & k) == 0)) {
-                        K[t] = d;
-                        K[o] = a;
-                        const uint16_t va = V[t];
-                        V[t] = V[o];
-                        V[o] = va;
-                    }
-                }
-            }
-            __syncthreads();
-        }
+    bitonic_sort<true>(K, V, n);
     for (int t = threadIdx.x; t < n; t += blockDim.x) {
         irow[b + t] = K[t];
         ival[b + t] = V[t];
     }
+}
+
+// The unsorted inverted index of V's N rows: off[0..N] and the entries irow / ival; cnt and cur
+// are N ints of scratch each.
+static int csc_build(const Rows& V, int64_t N, int32_t* cnt, int32_t* cur, int64_t* off, int32_t* irow,
+                     uint16_t* ival, hipStream_t s) {
+    RM_CHECK_HIP(hipMemsetAsync(cnt, 0, N * 4, s));
+    RM_CHECK_HIP(hipMemsetAsync(cur, 0, N * 4, s));
+    hipLaunchKernelGGL(csc_count_kernel, dim3((unsigned)N), dim3(256), 0, s, V, N, cnt);
+    RM_LAUNCHED();
+    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, cnt, N, off);
+    RM_LAUNCHED();
+    hipLaunchKernelGGL(csc_fill_kernel, dim3((unsigned)N), dim3(256), 0, s, V, N, (const int64_t*)off, cur, irow, ival);
+    RM_LAUNCHED();
+    return OK;
 }
 
 // ----------------------------------------------------------- R6 + R7: Jaccard
@@ -903,6 +823,23 @@ __global__ __launch_bounds__(256) void jaccard_bounds_kernel(const int64_t* __re
         lo = hi;  // every row index is < N
     }
     cbnd[t] = lo;
+}
+
+// The epilogue of both Jaccard kernels for one (query, chunk): tmin[t] (fp16 bits in LDS) is
+// temp_min of chunk column t, od[t] its unscaled original distance, dv the query's od divisor.
+// Jaccard in fp16 (every op rounded, reranking.py:93), the blend in fp32 (reranking.py:95).
+__device__ __forceinline__ void jaccard_blend(const uint16_t* tmin, int span, const float* __restrict__ od, float dv,
+                                              uint16_t lam16, float lam_f, float* __restrict__ out) {
+    const float lam = h2f_bits(lam16);
+    for (int t = threadIdx.x; t < span; t += blockDim.x) {
+        const float tv = h2f_bits(tmin[t]);
+        const uint16_t den = f2h_bits(2.0f - tv);
+        const uint16_t qt = f2h_bits(tv / h2f_bits(den));
+        const uint16_t jac = f2h_bits(1.0f - h2f_bits(qt));
+        const float a = h2f_bits(f2h_bits(h2f_bits(jac) * lam));
+        const float b = (od[t] / dv) * lam_f;
+        out[t] = a + b;
+    }
 }
 
 __global__ __launch_bounds__(256) void jaccard_kernel(const float* __restrict__ OD, int64_t ld, int64_t odc0,
@@ -969,18 +906,7 @@ __global__ __launch_bounds__(256) void jaccard_kernel(const float* __restrict__ 
             __syncthreads();
         }
     }
-    const float lam = h2f_bits(lam16);
-    const float dv = rowdiv[i];
-    for (int t = threadIdx.x; t < span; t += blockDim.x) {
-        const int64_t r = base + t;
-        const float tv = h2f_bits(tmin[t]);
-        const uint16_t den = f2h_bits(2.0f - tv);
-        const uint16_t qt = f2h_bits(tv / h2f_bits(den));
-        const uint16_t jac = f2h_bits(1.0f - h2f_bits(qt));
-        const float a = h2f_bits(f2h_bits(h2f_bits(jac) * lam));
-        const float b = (OD[y * ld + (r - odc0)] / dv) * lam_f;
-        out[y * ldo + (r - Q)] = a + b;
-    }
+    jaccard_blend(tmin, span, OD + y * ld + (base - odc0), rowdiv[i], lam16, lam_f, out + y * ldo + (base - Q));
 }
 
 // ---------------------------------------------------------------- workspace
@@ -992,8 +918,6 @@ struct RrPlan {
     QeSlab qe;
 };
 
-static int64_t al(int64_t v) { return (v + 255) & ~(int64_t)255; }
-
 // One-call driver: V and V_qe as ELL of their worst-case widths (rr_caps), so no row can
 // overflow; the generic kernels' slabs only when a row can need them.
 static RrPlan rr_plan(int64_t N, int k1, int k2, bool need_dist, bool need_t) {
@@ -1004,26 +928,26 @@ static RrPlan rr_plan(int64_t N, int k1, int k2, bool need_dist, bool need_t) {
     p.kr = kr_slab(c.kf, c.kh1);
     p.qe = qe_slab(c.k2e, c.tcap);
     int64_t o = 0;
-    p.dist = o; o = al(o + (need_dist ? N * N * 4 : 0) + (need_dist ? N * 4 : 0));
-    p.tdist = o; o = al(o + (need_t ? N * N * 4 : 0));
-    p.rowmax = o; o = al(o + N * 4);
-    p.rank = o; o = al(o + N * (int64_t)c.K * 4);
-    p.vcol = o; o = al(o + N * c.vcap * 4);
-    p.vval = o; o = al(o + N * c.vcap * 2);
-    p.vnnz = o; o = al(o + N * 4);
-    p.qcol = o; o = al(o + N * qw * 4);
-    p.qval = o; o = al(o + N * qw * 2);
-    p.qnnz = o; o = al(o + N * 4);
-    p.cnt = o; o = al(o + N * 4);
-    p.off = o; o = al(o + (N + 1) * 8);
-    p.cur = o; o = al(o + N * 4);
+    p.dist = o; o = align_up(o + (need_dist ? N * N * 4 : 0) + (need_dist ? N * 4 : 0), 256);
+    p.tdist = o; o = align_up(o + (need_t ? N * N * 4 : 0), 256);
+    p.rowmax = o; o = align_up(o + N * 4, 256);
+    p.rank = o; o = align_up(o + N * (int64_t)c.K * 4, 256);
+    p.vcol = o; o = align_up(o + N * c.vcap * 4, 256);
+    p.vval = o; o = align_up(o + N * c.vcap * 2, 256);
+    p.vnnz = o; o = align_up(o + N * 4, 256);
+    p.qcol = o; o = align_up(o + N * qw * 4, 256);
+    p.qval = o; o = align_up(o + N * qw * 2, 256);
+    p.qnnz = o; o = align_up(o + N * 4, 256);
+    p.cnt = o; o = align_up(o + N * 4, 256);
+    p.off = o; o = align_up(o + (N + 1) * 8, 256);
+    p.cur = o; o = align_up(o + N * 4, 256);
     const int64_t inv = k2 != 1 ? qw : c.vcap;  // inverted-index entries per row (upper bound)
-    p.irow = o; o = al(o + N * inv * 4);
-    p.ival = o; o = al(o + N * inv * 2);
-    p.dlist = o; o = al(o + N * 4);
-    p.dcount = o; o = al(o + 16);
-    p.krslab = o; o = al(o + (c.kr_fast ? 0 : GEN_WG * p.kr.bytes));
-    p.qeslab = o; o = al(o + (k2 != 1 ? GEN_WG * p.qe.bytes : 0));
+    p.irow = o; o = align_up(o + N * inv * 4, 256);
+    p.ival = o; o = align_up(o + N * inv * 2, 256);
+    p.dlist = o; o = align_up(o + N * 4, 256);
+    p.dcount = o; o = align_up(o + 16, 256);
+    p.krslab = o; o = align_up(o + (c.kr_fast ? 0 : GEN_WG * p.kr.bytes), 256);
+    p.qeslab = o; o = align_up(o + (k2 != 1 ? GEN_WG * p.qe.bytes : 0), 256);
     p.total = o;
     return p;
 }
@@ -1075,18 +999,7 @@ __global__ __launch_bounds__(256) void jaccard_scan_kernel(const float* __restri
         }
         __syncthreads();
     }
-    const float lam = h2f_bits(lam16);
-    const float dv = rowdiv[i];
-    for (int t = threadIdx.x; t < span; t += blockDim.x) {
-        const int64_t r = base + t;
-        const float tv = h2f_bits(tmin[t]);
-        const uint16_t den = f2h_bits(2.0f - tv);
-        const uint16_t qt = f2h_bits(tv / h2f_bits(den));
-        const uint16_t jac = f2h_bits(1.0f - h2f_bits(qt));
-        const float a = h2f_bits(f2h_bits(h2f_bits(jac) * lam));
-        const float b = (OD[i * ld + r] / dv) * lam_f;
-        out[i * ldo + (r - Q)] = a + b;
-    }
+    jaccard_blend(tmin, span, OD + i * ld + base, rowdiv[i], lam16, lam_f, out + i * ldo + (base - Q));
 }
 
 // od rows: OD (N x N, row i = distances from item i, scaled by 1/rowdiv[i] on the fly).
@@ -1104,14 +1017,14 @@ static int rerank_core(const float* OD, int64_t N, int64_t Q, int k1, int k2, ui
     int32_t* vnnz = (int32_t*)(ws + P.vnnz);
     const DistSrc ds{OD, N, 0, nullptr, 0, 0, nullptr};
     if ((rc = v_rows_launch(ds, rmax, R, c.K, 0, N, c, ws + P.krslab, vcol, vval, vnnz, flags, s))) return rc;
-    Rows Vq{nullptr, vnnz, c.vcap, vcol, vval};
+    const Rows V = ell_rows(vnnz, c.vcap, vcol, vval);
+    Rows Vq = V;  // (k2 = 1: V_qe = V)
     if (k2 != 1) {
         int32_t* qcol = (int32_t*)(ws + P.qcol);
         uint16_t* qval = (uint16_t*)(ws + P.qval);
         int32_t* qnnz = (int32_t*)(ws + P.qnnz);
         int32_t* dlist = (int32_t*)(ws + P.dlist);
         int32_t* dcount = (int32_t*)(ws + P.dcount);
-        const Rows V{nullptr, vnnz, c.vcap, vcol, vval};
         if (c.k2e <= QE_FAST_K2) {
             RM_CHECK_HIP(hipMemsetAsync(dcount, 0, 4, s));
             hipLaunchKernelGGL(qe_kernel, dim3((unsigned)N), dim3(256), 0, s, R, (int64_t)c.K, c.k2e, (int64_t)0, V, qcol,
@@ -1124,25 +1037,17 @@ static int rerank_core(const float* OD, int64_t N, int64_t Q, int k1, int k2, ui
                            c.k2e <= QE_FAST_K2 ? (const int32_t*)dcount : nullptr, N, 2, qcol,
                            qval, qnnz, c.qcap, (const int64_t*)nullptr, P.qe, ws + P.qeslab, c.tcap, flags);
         RM_LAUNCHED();
-        Vq = Rows{nullptr, qnnz, c.qcap, qcol, qval};
+        Vq = ell_rows(qnnz, c.qcap, qcol, qval);
     }
-    int32_t* cnt = (int32_t*)(ws + P.cnt);
     int64_t* off = (int64_t*)(ws + P.off);
-    int32_t* cur = (int32_t*)(ws + P.cur);
-    RM_CHECK_HIP(hipMemsetAsync(cnt, 0, N * 4, s));
-    RM_CHECK_HIP(hipMemsetAsync(cur, 0, N * 4, s));
-    hipLaunchKernelGGL(csc_count_kernel, dim3((unsigned)N), dim3(256), 0, s, Vq, N, cnt);
-    RM_LAUNCHED();
-    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, cnt, N, off);
-    RM_LAUNCHED();
-    hipLaunchKernelGGL(csc_fill_kernel, dim3((unsigned)N), dim3(256), 0, s, Vq, N, off, cur,
-                       (int32_t*)(ws + P.irow), (uint16_t*)(ws + P.ival));
-    RM_LAUNCHED();
+    int32_t* irow = (int32_t*)(ws + P.irow);
+    uint16_t* ival = (uint16_t*)(ws + P.ival);
+    if ((rc = csc_build(Vq, N, (int32_t*)(ws + P.cnt), (int32_t*)(ws + P.cur), off, irow, ival, s))) return rc;
     const int64_t G = N - Q;
     if (Q > 0 && G > 0) {
         dim3 grid(ceil_div(G, JCH), (unsigned)Q);
-        hipLaunchKernelGGL(jaccard_scan_kernel, grid, dim3(256), 0, s, OD, N, rmax, Q, N, Vq, off,
-                           (const int32_t*)(ws + P.irow), (const uint16_t*)(ws + P.ival), lam16, lam_f, out, ldo);
+        hipLaunchKernelGGL(jaccard_scan_kernel, grid, dim3(256), 0, s, OD, N, rmax, Q, N, Vq, (const int64_t*)off,
+                           (const int32_t*)irow, (const uint16_t*)ival, lam16, lam_f, out, ldo);
         RM_LAUNCHED();
     }
     return OK;
@@ -1762,7 +1667,7 @@ REIDMI_API int reidmi_rr_pack(const int32_t* ell_col, const uint16_t* ell_val, c
     RM_REQUIRE(rows >= 0 && cap > 0, "rr_pack: bad arguments");
     if (rows == 0) return OK;
     hipLaunchKernelGGL(rows_pack_kernel, dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream,
-                       Rows{nullptr, nnz, cap, ell_col, ell_val}, off, col, val);
+                       ell_rows(nnz, cap, ell_col, ell_val), off, col, val);
     RM_LAUNCHED();
     return OK;
 }
@@ -1781,7 +1686,7 @@ REIDMI_API int reidmi_rr_qe_rows(const int32_t* rank, int K, int k2, int64_t lo,
         RM_CHECK_HIP(hipMemsetAsync(dcount, 0, 4, s));
         if (n == 0) return OK;
         hipLaunchKernelGGL(qe_kernel, dim3((unsigned)n), dim3(256), 0, s, rank, (int64_t)K, k2, lo,
-                           Rows{voff, nullptr, 0, vcol, vval}, qcol, qval, qnnz, (int64_t)QCAP, dlist, dcount);
+                           csr_rows(voff, vcol, vval), qcol, qval, qnnz, (int64_t)QCAP, dlist, dcount);
         RM_LAUNCHED();
         return OK;
     }
@@ -1810,7 +1715,7 @@ REIDMI_API int reidmi_rr_qe_deferred(const int32_t* rank, int K, int k1, int k2,
     const QeSlab sl = qe_slab(k2, c.tcap);
     RM_REQUIRE(ws && ws_bytes >= GEN_WG * sl.bytes, "rr_qe_deferred: workspace of reidmi_rr_caps' qe_ws_bytes required");
     hipLaunchKernelGGL(qe_generic_kernel, dim3((unsigned)(n_def < GEN_WG ? n_def : GEN_WG)), dim3(256), 0,
-                       (hipStream_t)stream, rank, (int64_t)K, k2, lo, Rows{voff, nullptr, 0, vcol, vval}, dlist,
+                       (hipStream_t)stream, rank, (int64_t)K, k2, lo, csr_rows(voff, vcol, vval), dlist,
                        (const int32_t*)nullptr, n_def, mode, qcol, qval, qnnz, (int64_t)0, qoff, sl, (char*)ws, c.tcap,
                        flags);
     RM_LAUNCHED();
@@ -1824,10 +1729,10 @@ struct CscPlan {
 static CscPlan csc_plan(int64_t N, int64_t nnz) {
     CscPlan p{};
     int64_t o = 0;
-    p.cnt = o; o = al(o + N * 4);
-    p.cur = o; o = al(o + N * 4);
-    p.sk = o; o = al(o + 2 * nnz * 4);  // padded sort scratch of long lists
-    p.sv = o; o = al(o + 2 * nnz * 2);
+    p.cnt = o; o = align_up(o + N * 4, 256);
+    p.cur = o; o = align_up(o + N * 4, 256);
+    p.sk = o; o = align_up(o + 2 * nnz * 4, 256);  // padded sort scratch of long lists
+    p.sv = o; o = align_up(o + 2 * nnz * 2, 256);
     p.total = o;
     return p;
 }
@@ -1844,19 +1749,11 @@ REIDMI_API int reidmi_rr_csc(int64_t N, const int64_t* qoff, const int32_t* qcol
     RM_REQUIRE(ws_bytes >= P.total, "rr_csc: workspace too small");
     hipStream_t s = (hipStream_t)stream;
     char* ws = (char*)ws_;
-    const Rows V{qoff, nullptr, 0, qcol, qval};
-    int32_t* cnt = (int32_t*)(ws + P.cnt);
-    int32_t* cur = (int32_t*)(ws + P.cur);
-    RM_CHECK_HIP(hipMemsetAsync(cnt, 0, N * 4, s));
-    RM_CHECK_HIP(hipMemsetAsync(cur, 0, N * 4, s));
-    hipLaunchKernelGGL(csc_count_kernel, dim3((unsigned)N), dim3(256), 0, s, V, N, cnt);
-    RM_LAUNCHED();
-    hipLaunchKernelGGL(scan_kernel, dim3(1), dim3(1024), 0, s, cnt, N, coff);
-    RM_LAUNCHED();
+    int rc;
+    if ((rc = csc_build(csr_rows(qoff, qcol, qval), N, (int32_t*)(ws + P.cnt), (int32_t*)(ws + P.cur), coff, irow, ival,
+                        s)))
+        return rc;
     if (nnz == 0) return OK;
-    hipLaunchKernelGGL(csc_fill_kernel, dim3((unsigned)N), dim3(256), 0, s, V, N, (const int64_t*)coff, cur, irow,
-                       ival);
-    RM_LAUNCHED();
     hipLaunchKernelGGL(csc_sort_kernel, dim3((unsigned)N), dim3(256), 0, s, (const int64_t*)coff, irow, ival,
                        (int32_t*)(ws + P.sk), (uint16_t*)(ws + P.sv));
     RM_LAUNCHED();
@@ -1886,7 +1783,7 @@ REIDMI_API int reidmi_rr_jaccard_rows(const float* feat, int64_t N, int64_t D, i
                "rr_jaccard_rows: bad arguments");
     if (qhi == qlo || G == 0) return OK;
     hipStream_t s = (hipStream_t)stream;
-    const Rows Vq{qoff, nullptr, 0, qcol, qval};
+    const Rows Vq = csr_rows(qoff, qcol, qval);
     const int nch = ceil_div(G, JCH);
     RM_REQUIRE(bounds && ((uintptr_t)bounds & 7) == 0 && bounds_bytes >= jaccard_bounds_bytes(N, G),
                "rr_jaccard_rows: bounds of reidmi_rr_jaccard_bounds_bytes(N, N-Q) bytes (8-byte aligned) required");

@@ -89,7 +89,7 @@ def _groups(sizes, dim, noise, seed):
     return oracle.l2norm(f[r.permutation(len(f))])
 
 
-@pytest.mark.parametrize("case", ["k80_k40", "k150_k30_dense", "k20_k1030"])
+@pytest.mark.parametrize("case", ["k80_k40", "k150_k30_dense", "k20_k1030", "k260_k6"])
 def test_rerank_without_capacity_limits_vs_oracle(gpu, case):
     """The reference's re_ranking has no capacity limit (reranking.py:51-78: dense N x N V and
     V_qe); neither has this one.  Each case leaves the on-chip kernels:
@@ -99,7 +99,10 @@ def test_rerank_without_capacity_limits_vs_oracle(gpu, case):
                      stage more than the 6144 entries qe_kernel holds -> those rows deferred to
                      qe_generic_kernel, the rest on chip;
       k20_k1030      k2 = 1030: initial_rank prefix K = 1030 > 1024 (top-k in two rounds) and each
-                     V_qe row the mean of 1030 V rows (qe_generic_kernel's slab, ~30k entries).
+                     V_qe row the mean of 1030 V rows (qe_generic_kernel's slab, ~30k entries);
+      k260_k6        k1 = 260: k-reciprocal depth 261 > 256, so kreciprocal_generic_kernel's ballot
+                     loop takes a second pass, and groups of 270 give k-reciprocal sets of up to 261
+                     (a sorted copy wider than one pass of the workgroup).
     One-call (reidmi_rerank) and staged (reidmi_rr_*, deferred rows counted then written into
     the CSR) must both equal the oracle bit for bit."""
     rr = _rr()
@@ -109,9 +112,12 @@ def test_rerank_without_capacity_limits_vs_oracle(gpu, case):
     elif case == "k150_k30_dense":
         k1, k2, Q = 150, 30, 100
         f = _groups([300] * 6 + [40] * 10, 64, 0.2, 2)
-    else:
+    elif case == "k20_k1030":
         k1, k2, Q = 20, 1030, 60
         f = _groups([400] * 2 + [100] * 4, 32, 0.5, 3)
+    else:
+        k1, k2, Q = 260, 6, 60
+        f = _groups([270] * 2 + [30] * 4, 32, 0.5, 4)
     ref = oracle.re_ranking(f[:Q], f[Q:], k1, k2, 0.3)
     ft = torch.from_numpy(f).to(gpu)
     one = rr.re_ranking(ft[:Q], ft[Q:], k1, k2, 0.3)
