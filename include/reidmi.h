@@ -153,7 +153,7 @@ int reidmi_rr_feat16(const float* feat, int64_t N, int64_t D, int64_t ldf, void*
  * nmax2 of reidmi_rr_rank_rows_f16. */
 int reidmi_rr_norm_max(const float* sqn, const float* nrm, int64_t N, float* out2, void* stream);
 /* reidmi_rr_rank_rows with an fp16 MFMA pre-filter (same rank_out / rowmax_out bits): the fp16
- * product bounds every exact distance (error bound in backend.hip, above rank_select1_kernel); only the
+ * product bounds every exact distance (error bound in prefilter.hip, above rank_select1_kernel); only the
  * candidates are recomputed with the exact fp32 chain.  Default form (sample stride 16, for N
  * >= 4096): per-row thresholds from every 16th item, then the selection runs inside the GEMM's
  * epilogue (survivor lists, no N-wide row in HBM; when one call covers all N rows and the lists
@@ -169,7 +169,7 @@ int reidmi_rr_rank_rows_f16(const float* feat, int64_t N, int64_t D, int64_t ldf
                             int64_t chunk_rows, void* stream);
 /* The same with the sample stride chosen: 0 or 1 = the dense form (bounds written to the chunk,
  * streaming selection) at any N; S >= 2 = the selection inside the GEMM's epilogue against
- * per-row thresholds from every S-th item (backend.hip "R2 pre-filter with the selection in the
+ * per-row thresholds from every S-th item (prefilter.hip "R2 pre-filter with the selection in the
  * GEMM"), when floor(N / S) spans at least one 256-column tile and 4 K items (else the dense
  * form).  Same output bits.  reidmi_rr_rank_rows_f16 uses S = 16 (rerank.hip RR_SAMPLE_STRIDE):
  * 1M-item R2 1.98 s in the triangle form vs 3.9 s dense. */

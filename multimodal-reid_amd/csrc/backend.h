@@ -1,9 +1,25 @@
-// backend.h — what rerank.hip calls in backend.hip (internal, not part of the C ABI).
+// backend.h — the retrieval back end's internal launchers that another source calls, grouped by
+// the file that defines them (internal, not part of the C ABI).  Callers: rerank.hip, and
+// search.hip for the row norms.
 #pragma once
 #include "common.h"
 
 namespace reidmi {
 
+// distance.hip
+void rows_sqnorm_launch(const float* x, int64_t n, int64_t d, int64_t ld, float* out, hipStream_t s);
+int distmat_self_launch(const float* x, int64_t N, int64_t ldx, int64_t D, float* out, int64_t ldo, float* ws,
+                        hipStream_t s);
+int distmat_launch(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G, int64_t ldg, int64_t D,
+                   float* out, int64_t ldo, float* ws, hipStream_t s);
+int distmat_pre_launch(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G, int64_t ldg, int64_t D,
+                       const float* qq, const float* gg, float* out, int64_t ldo, hipStream_t s);
+
+// search.hip
+int topk_launch(const float* x, int64_t rows, int64_t cols, int64_t ldx, const float* row_div, int k,
+                int32_t* out_idx, float* out_val, int64_t ldo, hipStream_t s);
+
+// prefilter.hip
 int rank_select_launch(float* dot, int64_t ldd, const float* feat, int64_t ldf, int D, const float* sqn,
                        const float* nrm, const float* nmax2, int64_t row0, int64_t rows, int64_t N, int K,
                        int32_t* rank_out, float* rowmax_out, int32_t* need, hipStream_t s);
@@ -17,13 +33,5 @@ int rank_select_sv_launch(const int32_t* cnt, const int2* list, int cap, const f
                           float* rowmax_out, int32_t* need, hipStream_t s);
 int feat16_launch(const float* x, int64_t N, int64_t D, int64_t ldx, void* y, int64_t Np, int64_t Dp,
                   int32_t* range_ok, hipStream_t s);
-int topk_launch(const float* x, int64_t rows, int64_t cols, int64_t ldx, const float* row_div, int k,
-                int32_t* out_idx, float* out_val, int64_t ldo, hipStream_t s);
-int distmat_self_launch(const float* x, int64_t N, int64_t ldx, int64_t D, float* out, int64_t ldo, float* ws,
-                        hipStream_t s);
-int distmat_launch(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G, int64_t ldg, int64_t D,
-                   float* out, int64_t ldo, float* ws, hipStream_t s);
-int distmat_pre_launch(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G, int64_t ldg, int64_t D,
-                       const float* qq, const float* gg, float* out, int64_t ldo, hipStream_t s);
 
 }  // namespace reidmi

@@ -67,7 +67,7 @@ REIDMI_API int reidmi_distmat_f16(const float* q, int64_t Q, int64_t ldq, const 
     hipLaunchKernelGGL(rows_to_f16_kernel, dim3((unsigned)p.Gp), dim3(256), 0, s, g, G, D, ldg, gh, p.Dp);
     RM_LAUNCHED();
     int rc;
-    // exact fp32 squared norms (backend.hip's fmaf chain over k)
+    // exact fp32 squared norms (distance.hip's fmaf chain over k)
     if ((rc = reidmi_row_sqnorm_f32(q, Q, D, ldq, qq, stream))) return rc;
     if ((rc = reidmi_row_sqnorm_f32(g, G, D, ldg, gg, stream))) return rc;
     // the products and the distance in one pass: the GEMM's epilogue writes

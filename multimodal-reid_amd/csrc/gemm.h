@@ -64,7 +64,7 @@ struct EpiArgs {
     float2* pstat;
     int64_t ldp;
     // EPI_RRHI: row m is item rr_row0 + m, column n item n (n >= rr_n: +inf); squared norms and
-    // norms of the items; the bound's constants (c_rel, c_abs, c_d: backend.hip rank_select)
+    // norms of the items; the bound's constants (c_rel, c_abs, c_d: prefilter.hip rank_select)
     const float* rr_sqn;
     const float* rr_nrm;
     int64_t rr_row0;
@@ -99,7 +99,7 @@ struct EpiArgs {
 
 // hi(i, j) = fl(dt + e), dt = fl(fma(-2, dot, s_i + s_j)),
 // e = 1.01 (fma(c_rel n_i, n_j, 2^-23 (s_i + s_j)) + c_abs (n_i + n_j) + c_d): the exact fp32
-// distance of i and j is <= hi and >= fl(dt - e) (backend.hip rank_select).  One definition for
+// distance of i and j is <= hi and >= fl(dt - e) (prefilter.hip rank_select).  One definition for
 // the GEMM epilogue and the selection's re-evaluation of single pairs.
 __device__ __forceinline__ float rr_hi(float dot, float si, float sj, float crn_i, float ni, float nj,
                                        const float (&c)[3]) {

@@ -1,7 +1,7 @@
 // rerank.hip — k-reciprocal re-ranking (reranking.py:29-100, Zhong et al. CVPR'17) on gfx950.
 //
 // Stage map, all bit-exact with oracle/reid_oracle.c:
-//   R1 distmat over cat(q, g)                    backend.hip distmat (exact fp32)      reranking.py:36-41
+//   R1 distmat over cat(q, g)                    distance.hip distmat (exact fp32)     reranking.py:36-41
 //   R2 od = D / colmax, initial_rank[:, :K]      rowmax + topk (stable ties)           reranking.py:45-48
 //   R3 k-reciprocal expansion + V row            kreciprocal_kernel  (ELL, fp16)       reranking.py:51-71
 //   R4 query expansion V_qe = mean of k2 rows    qe_kernel            (ELL, fp16)      reranking.py:73-78
@@ -230,7 +230,7 @@ static Rows ell_rows(const int32_t* nnz, int64_t cap, const int32_t* col, const 
 // Where original_dist entries come from: a materialised matrix (od != nullptr: entry
 // (i, c) = od[(i - row0) * ld + c]) or recomputed from the features with the distance
 // kernel's exact arithmetic — an fmaf chain over k ascending, then fmaf(-2, dot, |i|^2 +
-// |c|^2) (backend.hip distmat_f32_kernel; the fp32 MFMA accumulates in the same order).
+// |c|^2) (distance.hip distmat_f32_kernel; the fp32 MFMA accumulates in the same order).
 #ifndef DA_UNROLL
 #define DA_UNROLL 16
 #endif
@@ -1202,7 +1202,7 @@ REIDMI_API int reidmi_rr_norm_max(const float* sqn, const float* nrm, int64_t N,
     return norm_max_launch(sqn, nrm, N, out2, (hipStream_t)stream);
 }
 
-// Sampled survivor form of the pre-filter (backend.hip rr_sample_kernel / rank_select_sv_kernel):
+// Sampled survivor form of the pre-filter (prefilter.hip rr_sample_kernel / rank_select_sv_kernel):
 // the sample is every S-th item, ns = floor(N / S) rounded down to whole 256-column tiles; per
 // row: the sample's bounds, then the survivor list (RR_SV_CAP pairs) instead of an N-wide row.
 // The selection runs inside the GEMM's epilogue (gemm.hip rrsv_tile): survivors staged in LDS,
@@ -1473,7 +1473,7 @@ static int rank_rows_f16(const float* feat, int64_t N, int64_t D, int64_t ldf, c
 // need[r] = 0; rows with need[r] = 1 (concentrated or non-finite distances) are left for the
 // exact rows.  nrm = sqrt(sqn) [N]; nmax2 = reidmi_rr_norm_max of sqn, nrm.  chunk: chunk_rows x
 // Np fp32 of scratch.  Default: sample stride RR_SAMPLE_STRIDE (16), the selection inside the
-// GEMM's epilogue (backend.hip, "R2 pre-filter with the selection in the GEMM"; the triangle
+// GEMM's epilogue (prefilter.hip, "R2 pre-filter with the selection in the GEMM"; the triangle
 // form when one call covers all rows); below that size, or with reidmi_rr_rank_rows_f16_ex's
 // stride 0 / 1, the GEMM writes the rows' bounds (chunk_rows x Np) and rank_select1 streams them.
 // Same bits either way.

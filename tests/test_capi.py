@@ -62,7 +62,8 @@ def test_tools_library_exports_variants_product_does_not():
 
 @pytest.mark.parametrize("src,define", [("gemm.hip", "-DGEMM_VAR_NOSTORE=1"), ("gemm.hip", "-DGEMM_VAR_NOWAIT=1"),
                                         ("gemm.hip", "-DGEMM_VAR_NODMA=1"),
-                                        ("backend.hip", "-DDM2_BK_=32"), ("backend.hip", "-DRS_STATS")])
+                                        ("distance.hip", "-DDM2_BK_=32"), ("search.hip", "-DDM2_BK_=32"),
+                                        ("prefilter.hip", "-DRS_STATS")])
 def test_variant_macros_refused_outside_tools_builds(src, define):
     """The A/B timing hooks (some compile kernels with wrong results by design) are an #error
     unless the tools define is set, so no variant can be built into libreidmi.so."""

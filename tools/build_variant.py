@@ -18,7 +18,7 @@ def main():
     out_dir = os.path.join(ROOT, "tools", "variants")
     os.makedirs(out_dir, exist_ok=True)
     obj = os.path.join(out_dir, f"{name}_{src.replace('.hip', '.o')}")
-    # -DREIDMI_TOOLS: the variant macros are refused without it (gemm.hip / backend.hip #error)
+    # -DREIDMI_TOOLS: the variant macros are refused without it (gemm.hip / distance.h / prefilter.hip #error)
     r = subprocess.run([B.HIPCC, *B.FLAGS, B.TOOLS_DEFINE, *defs, "-c", os.path.join(B.CSRC, src), "-o", obj],
                        capture_output=True, text=True)
     if r.returncode:
