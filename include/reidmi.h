@@ -326,6 +326,21 @@ int reidmi_attn_lpad(int L);
 int reidmi_mhsa_f16(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H, int causal,
                      void* stream);
 
+/* Row length of v^T for an L-token sequence, 1 <= L <= 1024: 32 * ceil(L / 32) + 4, the rule of
+ * reidmi_attn_lpad continued past 256 (equal to it up to 256); negative otherwise. */
+int reidmi_attn_vt_stride(int L);
+
+/* The same non-causal SDPA for sequences of up to 1024 tokens (the vision tower on square and
+ * large crops: 224 x 224 -> 325 tokens, 256 x 256 -> 442, 384 x 384 -> 962).  K and v^T stream
+ * through LDS in 64-key tiles with a running row max and sum (online softmax); rounding points
+ * as reidmi_mhsa_f16 (fp32 scores, sums and accumulation; P and O rounded to fp16 once).
+ * q,k [nseq*H][L][64], vt [nseq*H][64][reidmi_attn_vt_stride(L)], o [nseq*L][H*64]; all fp16,
+ * 16-byte aligned.  1 <= L <= 1024.  v^T columns >= L may hold anything (never used); nothing is
+ * read behind the last head's K rows or v^T row.  reidmi_vit_forward uses it above 256 tokens
+ * and reidmi_mhsa_f16 up to 256. */
+int reidmi_mhsa_long_f16(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H,
+                         void* stream);
+
 /* LayerNorm over rows of width W in {512,768,1024} (fp32 math, eps) — custom_clip_model.py:43-49.
  * Row r of the output reads input row row_idx ? row_idx[r] : r.  y32 / y16 (fp16) nullable. */
 int reidmi_layernorm(const float* x, int64_t rows, int64_t ldx, const int32_t* row_idx, int64_t W,
@@ -395,12 +410,14 @@ typedef struct reidmi_vit_weights {
     const reidmi_block_weights* blocks;
 } reidmi_vit_weights;
 
-/* Workspace bytes for reidmi_vit_forward at batch B (full = 0: CLS outputs only). */
+/* Workspace bytes for reidmi_vit_forward at batch B (full = 0: CLS outputs only); -1 for bad
+ * weights or more than 1024 tokens (1 + grid_h * grid_w + n_ctx). */
 int64_t reidmi_vit_workspace_bytes(const reidmi_vit_weights* w, int64_t B, int full);
 
 /* encode_image: runs resblocks[:11] then resblocks[11] (custom_clip_model.py:91-92, also for
  * deeper towers), ln_post and proj.  images [B][3][H][Wimg] fp32 (images_f16 = 0) or fp16,
- * already normalised.  tta (nullable, device int32 [B][2]): apply the augmented loader's
+ * already normalised; any grid of at most 1024 tokens (1 + grid_h * grid_w + n_ctx: 256 x 128
+ * -> 211, 224 x 224 -> 325, 256 x 256 -> 442, 384 x 384 -> 962 at patch 16, stride 12).  tta (nullable, device int32 [B][2]): apply the augmented loader's
  * flip + Pad((10,5)) + crop at (top, left) on the fly (data_prepare.py:263-270).
  * full = 0: out_x12 [B][W] = ln_post(x12)[:,0], out_proj [B][E] = (x12 @ proj)[:,0],
  *           out_x11 [B][W] = x11[:,0] (nullable)          (zero_shot_learning.py:84-87)

@@ -61,6 +61,13 @@ int reidmi_mhsa_f16_rr(const void* q, const void* k, const void* vt, void* o, in
 int reidmi_mhsa_cls_f16(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H,
                         void* stream);
 
+/* The single-query (CLS) attention of the K / V path beyond 256 tokens (mhsa_cls_long_kernel:
+ * the same arithmetic with the keys walked in chunks), 1 <= L <= 1024, vt rows of
+ * reidmi_attn_vt_stride(L) (columns >= L never used; no piece is read past a row's end)
+ * -> o [nseq][H*64] fp16. */
+int reidmi_mhsa_cls_long_f16(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H,
+                             void* stream);
+
 /* The last block's CLS attention without K and V (cls_u_kernel, cls_attn_kernel, cls_o_kernel;
  * attention.hip): x [nseq*L][W] fp16 (the block's ln_1 input), rs [nseq*L][2] fp32 = (rstd, -mean
  * rstd) of its rows (reidmi_row_stats_f16), q [nseq][W] fp16 (the CLS queries, head-major), wqkv

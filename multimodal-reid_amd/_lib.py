@@ -73,6 +73,8 @@ SIGNATURES = {
     "reidmi_nonzero_i32": [_vp, _i64, _vp, _vp, _vp],
     "reidmi_gather_rows_f32": [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp],
     "reidmi_attn_lpad": [_i32],
+    "reidmi_attn_vt_stride": [_i32],
+    "reidmi_mhsa_long_f16": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp],
     "reidmi_prof_enable": [_i32],
     "reidmi_prof_collect": [_i32, _vp, _vp, _vp],
     "reidmi_prof_collect_min": [_i32, ctypes.c_double, _vp, _vp, _vp],
@@ -110,6 +112,7 @@ TOOLS_SIGNATURES = {
     "reidmi_gemm_f16_qkv": [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp],
     "reidmi_mhsa_f16_rr": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp],
     "reidmi_mhsa_cls_f16": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp],
+    "reidmi_mhsa_cls_long_f16": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp],
     "reidmi_cls_attn_nokv_ws_bytes": [_i64, _i32],
     "reidmi_cls_attn_nokv_f16": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp],
     "reidmi_gemm_f16_qkv_ex": [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32,

@@ -10,7 +10,7 @@
 // Inputs from the QKV GEMM epilogue: q,k [B*H][L][64] fp16, vt [B*H][64][Lp] fp16 (the
 // reference's GPU dtype); P is rounded to fp16 for the P.V MFMAs.
 // Output o [B*L][H*64] fp16 (token-major: the A operand of out_proj).
-#include "common.h"
+#include "attention.h"
 
 #include <type_traits>
 
@@ -22,40 +22,7 @@ __device__ __forceinline__ uint32_t lds_addr(const void* p) {
     return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
 }
 
-__device__ __forceinline__ int kswz(int r, int kc) { return r * 64 + ((kc ^ ((r >> 1) & 7)) << 3); }
-
 typedef __attribute__((address_space(3))) void* lds_ptr_t;
-typedef float f32x2v __attribute__((ext_vector_type(2)));
-typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));
-
-// fp32 -> fp16 (RNE) of a value that must be rounded to fp32 first: the opaque copy keeps the
-// backend from merging the fma that produced x and this conversion into one v_fma_mixlo_f16
-// (a single rounding to fp16, which differs from gemm.hip's in about 1 value in 1500)
-__device__ __forceinline__ _Float16 f32_to_h(float x) {
-    asm("" : "+v"(x));
-    return (_Float16)x;
-}
-
-// one v_cvt_pk_f16_f32 (RNE) per pair, as gemm.hip's epilogues convert
-__device__ __forceinline__ uint32_t cvt_pk_h(float a, float b) {
-    return __builtin_bit_cast(uint32_t, __builtin_convertvector(f32x2v{a, b}, f16x2v));
-}
-
-// fp16 pair (a * inv, b * inv), each product rounded to fp16 ONCE (v_fma_mixlo / mixhi: the
-// exact product, one rounding).  Left to itself the backend lowers (_Float16)(a * inv) as a
-// mix instruction for some elements and as v_mul + v_cvt_pk (two roundings) for others, so
-// the two attention blocks would differ in ~1 value in 36 000.
-__device__ __forceinline__ uint32_t mul_pk_h(float a, float b, float inv) {
-#ifdef ATTN_OUT_CVT  // A/B only: fp32 product, then RNE to fp16 (two roundings)
-    float x = a * inv, y = b * inv;
-    asm("" : "+v"(x), "+v"(y));
-    return cvt_pk_h(x, y);
-#endif
-    uint32_t r;
-    asm("v_fma_mixlo_f16 %0, %1, %2, 0" : "=v"(r) : "v"(a), "v"(inv));
-    asm("v_fma_mixhi_f16 %0, %1, %2, 0" : "+v"(r) : "v"(b), "v"(inv));
-    return r;
-}
 
 // One wave's block of 32 queries (row qi = block * 32 + (lane & 31)) against the head's K
 // [LP][64] and V^T [64][vstride] in LDS:
@@ -159,8 +126,8 @@ __device__ __forceinline__ void attn_block(const _Float16* sK, const _Float16* s
 //  * the cross-half exchanges (max, sum) use v_permlane32_swap: no LDS op of the compiler's
 //    own in the block, so the counted waits are exact.
 //  * O^T is widened to 16-byte stores by one v_permlane32_swap per dword (4 stores per lane
-//    instead of 8 half-width ones): kAttnPipeStores vector-memory ops per wave.
-constexpr int kAttnPipeStores = 4;
+//    instead of 8 half-width ones): kAttnPipeStores vector-memory ops per wave (store_o_wide,
+//    attention.h).
 
 template <int I, int N, typename F>
 __device__ __forceinline__ void static_for(F&& f) {
@@ -183,27 +150,6 @@ template <int N>
 __device__ __forceinline__ void lgkm_wait4(f16x8& a, f16x8& b, f16x8& c, f16x8& d) {
     asm volatile("s_waitcnt lgkmcnt(%4)" : "+v"(a), "+v"(b), "+v"(c), "+v"(d) : "n"(N) : "memory");
 }
-// {x[l], x[l ^ 32]} in some order per lane.  The results are copied out as uint32_t before any
-// bit_cast: hipcc 7.2 lowers __builtin_bit_cast(float, r[1]) applied to the builtin's vector
-// result as element 0 (both results then read the first register).
-__device__ __forceinline__ void xhalf_pair(float x, float& a, float& b) {
-    const uint32_t u = __builtin_bit_cast(uint32_t, x);
-    const auto r = __builtin_amdgcn_permlane32_swap(u, u, false, false);
-    const uint32_t r0 = r[0], r1 = r[1];
-    a = __builtin_bit_cast(float, r0);
-    b = __builtin_bit_cast(float, r1);
-}
-__device__ __forceinline__ float xhalf_max(float x) {  // max(x[l], x[l ^ 32])
-    float a, b;
-    xhalf_pair(x, a, b);
-    return fmaxf(a, b);
-}
-__device__ __forceinline__ float xhalf_sum(float x) {  // x[l] + x[l ^ 32] (commutative: = x + shfl_xor(x, 32))
-    float a, b;
-    xhalf_pair(x, a, b);
-    return a + b;
-}
-
 // mid(): called once in the P.V phase (after block NKB/2's MFMAs), after(): right after the
 // last P.V MFMA, before the O stores — the caller's prefetch for the next head goes there.
 template <int NKB, int VS_ = NKB * 32 + 4, typename Mid, typename After>
@@ -343,28 +289,7 @@ __device__ __forceinline__ void attn_block_pipe(const _Float16* sK, const _Float
     after();
     const float sum = xhalf_sum(sum2.x + sum2.y);
     const float inv = 1.0f / sum;
-    // lane (ql, hh) holds d = db*32 + 8g + 4hh + 0..3; pair g = 2j, 2j+1 across the halves so
-    // that half 0 stores d 16j..16j+7 and half 1 d 16j+8..16j+15 (16 bytes each)
-    uint4 w[2][2];
-#pragma unroll
-    for (int db = 0; db < 2; db++)
-#pragma unroll
-        for (int j = 0; j < 2; j++) {
-            const int g0 = 2 * j, g1 = 2 * j + 1;
-            auto pk = [&](int e) { return mul_pk_h(oacc[db][e], oacc[db][e + 1], inv); };
-            const uint32_t x0 = pk(4 * g0), x1 = pk(4 * g0 + 2), y0 = pk(4 * g1), y1 = pk(4 * g1 + 2);
-            const auto r0 = __builtin_amdgcn_permlane32_swap(x0, y0, false, false);
-            const auto r1 = __builtin_amdgcn_permlane32_swap(x1, y1, false, false);
-            w[db][j] = make_uint4(r0[0], r1[0], r0[1], r1[1]);
-        }
-    if (qi < L) {
-        const int64_t b = bh / H, hd = bh % H;
-        _Float16* orow = o + (b * L + qi) * (int64_t)(H * 64) + hd * 64 + 8 * hh;
-#pragma unroll
-        for (int db = 0; db < 2; db++)
-#pragma unroll
-            for (int j = 0; j < 2; j++) *(uint4*)(orow + db * 32 + 16 * j) = w[db][j];
-    }
+    store_o_wide(oacc, inv, qi, hh, L, bh, H, o);
 }
 
 // Persistent: gridDim.x workgroups (one per CU) walk the (sequence, head) pairs; one wave

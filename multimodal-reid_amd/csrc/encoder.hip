@@ -21,6 +21,10 @@ namespace reidmi {
 int mhsa(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H, bool causal,
          hipStream_t s);
 int attn_lpad(int L);
+// attention_long.hip: the streamed-key kernels for 256 < L <= 1024 (vision only, non-causal)
+int attn_vt_stride(int L);
+int mhsa_long(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H, hipStream_t s);
+int mhsa_cls_long(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H, hipStream_t s);
 int mhsa_cls(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H, hipStream_t s);
 int64_t cls_attn_nokv_ws_bytes(int64_t nseq, int W);
 int cls_attn_nokv(const void* x, const void* rs, const void* q, const void* wqkv, const float* colsum,
@@ -498,6 +502,10 @@ static int ln1_stats(XStats xs, char* ws, const Plan& P, int64_t M, int W, hipSt
     return row_stats((const _Float16*)(ws + P.x), M, W, W, st, s);
 }
 
+// Longest sequence of attention.hip's whole-head kernels (mhsa, mhsa_cls); longer ones, up to
+// attn_vt_stride's 1024, take attention_long.hip's streamed-key kernels.
+constexpr int kAttnShortMax = 256;
+
 // One ResidualAttentionBlock on the fp16 residual stream x [nseq*L][W].  ln_1 / ln_2 are
 // folded into the QKV / c_fc GEMMs (fp16 operands: x itself and W diag(gamma)); only the
 // per-row statistics are computed here (row_stats), never the normalised activations.
@@ -524,9 +532,14 @@ static int run_block(const reidmi_block_weights& bw, char* ws, const Plan& P, in
         ea.vt = ws + P.vt;
         ea.seq = L;
         ea.heads = H;
-        ea.lpad = attn_lpad(L);
+        ea.lpad = attn_vt_stride(L);  // (= attn_lpad(L) up to 256 tokens)
         if ((rc = gemm_f16(EPI_QKV, x, W, bw.qkv_w, W, M, 3 * W, W, ea, s))) return rc;
-        if ((rc = mhsa(ws + P.q, ws + P.k, ws + P.vt, o, nseq, L, H, causal, s))) return rc;
+        if (L <= kAttnShortMax) {
+            if ((rc = mhsa(ws + P.q, ws + P.k, ws + P.vt, o, nseq, L, H, causal, s))) return rc;
+        } else {
+            RM_REQUIRE(!causal, "run_block: no causal attention beyond 256 tokens");
+            if ((rc = mhsa_long(ws + P.q, ws + P.k, ws + P.vt, o, nseq, L, H, s))) return rc;
+        }
     }
     EpiArgs er{};
     er.out = x;
@@ -585,7 +598,8 @@ static int run_block_cls(const reidmi_block_weights& bw, char* ws, const Plan& P
     RM_LAUNCHED();
     // the reassociated path covers widths 768 / 1024 (64-wide heads), L <= 224 and scratch that
     // fits the K buffer of the other path (L * W * 2 bytes per image); anything else (and
-    // REIDMI_CLS_KV=1, read per call: tests switch it in-process) takes the K / V path
+    // REIDMI_CLS_KV=1, read per call: tests switch it in-process) takes the K / V path, whose
+    // single-query kernel is mhsa_cls up to 256 tokens and mhsa_cls_long beyond
     const char* kv_env = getenv("REIDMI_CLS_KV");
     const bool kv_path = (kv_env != nullptr && kv_env[0] == '1') || !(W == 768 || W == 1024) || H * 64 != W ||
                          L > 224 || cls_attn_nokv_ws_bytes(nseq, W) > nseq * L * W * 2;
@@ -610,12 +624,14 @@ static int run_block_cls(const reidmi_block_weights& bw, char* ws, const Plan& P
         kv.vt = ws + P.vt;
         kv.seq = L;
         kv.heads = H;
-        kv.lpad = attn_lpad(L);
+        kv.lpad = attn_vt_stride(L);  // (= attn_lpad(L) up to 256 tokens)
         kv.n_off = W;
         if ((rc = gemm_f16(EPI_QKV, x, W, (const _Float16*)bw.qkv_w + (int64_t)W * W, W, M, 2 * W, W, kv, s)))
             return rc;
         if ((rc = gemm_f16(EPI_QKV, x, ldc, bw.qkv_w, W, nseq, W, W, qa, s))) return rc;
-        if ((rc = mhsa_cls(ws + P.q, ws + P.k, ws + P.vt, o, nseq, L, H, s))) return rc;
+        if (L <= kAttnShortMax) rc = mhsa_cls(ws + P.q, ws + P.k, ws + P.vt, o, nseq, L, H, s);
+        else rc = mhsa_cls_long(ws + P.q, ws + P.k, ws + P.vt, o, nseq, L, H, s);
+        if (rc) return rc;
     }
     EpiArgs er{};
     er.out = x;
@@ -659,8 +675,9 @@ REIDMI_API int reidmi_layernorm(const float* x, int64_t rows, int64_t ldx, const
 
 REIDMI_API int64_t reidmi_vit_workspace_bytes(const reidmi_vit_weights* w, int64_t B, int full) {
     if (vit_check(w)) return -1;
-    const int L = 1 + w->grid_h * w->grid_w + w->n_ctx;
-    return plan(B, L, w->width, attn_lpad(L), 0).total;
+    const int64_t L = 1 + (int64_t)w->grid_h * w->grid_w + w->n_ctx;
+    if (L < 1 || L > 1024) return -1;  // (attn_vt_stride's range)
+    return plan(B, (int)L, w->width, attn_vt_stride((int)L), 0).total;
 }
 
 REIDMI_API int reidmi_vit_forward(const reidmi_vit_weights* w, const void* images, int images_f16, int64_t B, int H,
@@ -669,11 +686,11 @@ REIDMI_API int reidmi_vit_forward(const reidmi_vit_weights* w, const void* image
     int rc;
     if ((rc = vit_check(w))) return rc;
     hipStream_t s = (hipStream_t)stream;
+    RM_REQUIRE(1 + (int64_t)w->grid_h * w->grid_w + w->n_ctx <= 1024, "vit: too many tokens (max 1024)");
     const int W = w->width, NP = w->grid_h * w->grid_w, L = 1 + NP + w->n_ctx, E = w->out_dim;
     RM_REQUIRE((H - w->patch) / w->stride + 1 == w->grid_h && (Wimg - w->patch) / w->stride + 1 == w->grid_w,
                "vit: image size does not match the positional-embedding grid");
-    RM_REQUIRE(attn_lpad(L) > 0, "vit: too many tokens (max 256)");
-    const Plan P = plan(B, L, W, attn_lpad(L), 0);
+    const Plan P = plan(B, L, W, attn_vt_stride(L), 0);
     RM_REQUIRE(ws_bytes >= P.total, "vit: workspace too small");
     RM_REQUIRE(out_x12 && out_proj, "vit: outputs required");
     if (B == 0) return OK;

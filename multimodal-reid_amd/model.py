@@ -171,7 +171,8 @@ def resize_pos_embed(posemb, gh, gw):
 
 class VisionTransformer:
     """libreidmi vision tower.  ``stride`` defaults to the CLIP-ReID value 12
-    (utils.py:169).  ``height``/``width`` are the input crop size (256x128)."""
+    (utils.py:169).  ``height``/``width`` are the input crop size: 256x128 by default, any crop
+    of up to 1024 tokens (1 + grid + prompt rows; 224x224 -> 325, 256x256 -> 442, 384x384 -> 962)."""
 
     def __init__(self, state_dict, height=256, width=128, stride=12, device=None, prefix=""):
         sd = {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)}
