@@ -518,6 +518,127 @@ int64_t reidmi_text_pack_bytes(const reidmi_text_src* src);
 int reidmi_text_weights_pack(const reidmi_text_src* src, void* buf, int64_t buf_bytes, reidmi_text_weights* out,
                              reidmi_block_weights* out_blocks, void* stream);
 
+/* ------------------------------------------------ ResNet image tower (RN50 / RN101, resnet.hip)
+ *
+ * custom_clip_model.ModifiedResNet (custom_clip_model.py:186-242), eval mode, the reference's GPU
+ * dtype: activations fp16 NHWC in HBM, convolution weights the fp16 cast of the checkpoint's
+ * (utils.py:145-166), fp32 accumulation on v_mfma_f32_16x16x32_f16.  BatchNorm is NOT folded into
+ * the fp16 weights: it is the fp32 epilogue acc * s_c + t_c with s = gamma / sqrt(var + 1e-5),
+ * t = beta - mean * s (fp64 at pack time, stored fp32); then the residual is added in fp32, ReLU
+ * applied, and the value rounded to fp16 once. */
+
+/* y = relu?(conv(x, w) * scale + shift (+ resid)): implicit-GEMM convolution, M = B * Ho * Wo
+ * output pixels, N = Cout, K = k * k * Cin; per output element one chain over the taps (ky, kx)
+ * ascending, then channels ascending; out-of-image taps read as zero.
+ * x [B][H][W][Cin], y and resid (nullable) [B][Ho][Wo][Cout] fp16, Ho = (H + 2 pad - k) / stride + 1,
+ * pad = k / 2; w [Cout][k][k][Cin] fp16; scale, shift [Cout] fp32; 16-byte aligned.
+ * k in {1, 3}, stride in {1, 2}, Cout % 32 == 0, and Cin % 32 == 0 (the MFMA kernel) or Cin == 3
+ * with k == 3 and Cout <= 512 (the stem's first convolution: its own small fp32 kernel). */
+int reidmi_conv2d_f16(const void* x, int64_t B, int H, int W, int Cin, const void* w, int Cout, int k, int stride,
+                      const float* scale, const float* shift, const void* resid, int relu, void* y, void* stream);
+
+/* nn.AvgPool2d(2) on NHWC fp16: y[b][i][j][c] = fp16(((x00 + x01) + x10 + x11) * 0.25) with the
+ * sum in fp32 in that order (x00 = x[b][2i][2j][c], x01 its right, x10 / x11 the row below), one
+ * rounding.  x [B][H][W][C], y [B][H/2][W/2][C]; H, W even, C % 8 == 0. */
+int reidmi_avgpool2_f16(const void* x, int64_t B, int H, int W, int C, void* y, void* stream);
+
+/* One convolution + BatchNorm of the packed tower: w [cout][k][k][cin] fp16, scale / shift fp32. */
+typedef struct reidmi_conv_weights {
+    const void* w;
+    const float* scale;
+    const float* shift;
+    int32_t cin, cout, k, stride;
+} reidmi_conv_weights;
+
+/* Bottleneck (custom_clip_model.py:103-146): conv1 1x1, conv2 3x3, AvgPool2d(stride) when
+ * stride > 1, conv3 1x1, + identity (through AvgPool2d(stride) -> down 1x1 -> BN when has_down). */
+typedef struct reidmi_bottleneck_weights {
+    reidmi_conv_weights conv1, conv2, conv3, down;
+    int32_t stride, has_down;
+} reidmi_bottleneck_weights;
+
+/* The packed tower.  width = the stem width w (64 for RN50 / RN101); embed = 32 w (the pooled
+ * feature width); heads = embed / 64; layers = block counts of layer1..4 (layer2, layer3 stride 2,
+ * layer4 stride 1: x4 stays at H/16 x W/16); grid = the attention pool's positional grid
+ * (H / 16, W / 16).  pos_emb [1 + grid_h * grid_w][embed] fp32; qkv_w = [q; k; v]_proj.weight
+ * [3 embed][embed] fp16, qkv_b [3 embed] fp32; c_w = c_proj.weight [out_dim][embed] fp16, c_b
+ * [out_dim] fp32.  blocks: HOST array of layers[0] + .. + layers[3] entries.  tta_pad: the value
+ * of a padded pixel of the TTA view per channel, i.e. what a zero pixel becomes under the
+ * loader's Normalize, (0 - mean_c) / std_c; the packer sets -1 (Normalize(0.5, 0.5)), a caller
+ * with other statistics (ImageNet's, data_prepare.py:268) overwrites it. */
+typedef struct reidmi_resnet_weights {
+    int32_t width, embed, heads, out_dim, grid_h, grid_w;
+    int32_t layers[4];
+    reidmi_conv_weights stem[3];
+    const float* pos_emb;
+    const void* qkv_w;
+    const float* qkv_b;
+    const void* c_w;
+    const float* c_b;
+    const reidmi_bottleneck_weights* blocks;
+    float tta_pad[3];
+} reidmi_resnet_weights;
+
+/* The reference's key layout (fp32 device tensors): conv{i}.weight [Cout][Cin][k][k] with
+ * bn{i}.{weight, bias, running_mean, running_var}. */
+typedef struct reidmi_convbn_src {
+    const float* conv_w;
+    const float* bn_w;
+    const float* bn_b;
+    const float* bn_mean;
+    const float* bn_var;
+} reidmi_convbn_src;
+
+/* layer{l}.{i}.conv{1..3} / bn{1..3} and downsample.{0,1} (down.conv_w NULL: no downsample). */
+typedef struct reidmi_bottleneck_src {
+    reidmi_convbn_src conv1, conv2, conv3, down;
+} reidmi_bottleneck_src;
+
+/* conv1..3 / bn1..3 (stem), layer1..4, attnpool.{positional_embedding [1 + grid_h * grid_w][32 w]
+ * (already at the H/16 x W/16 grid: utils.resize_pos_embed otherwise, utils.py:228-231), q_proj,
+ * k_proj, v_proj, c_proj (.weight [out][in], .bias)}.  blocks: HOST array, layer1's first. */
+typedef struct reidmi_resnet_src {
+    int32_t width, out_dim, grid_h, grid_w;
+    int32_t layers[4];
+    reidmi_convbn_src stem[3];
+    const float* positional_embedding;
+    const float* q_w;
+    const float* q_b;
+    const float* k_w;
+    const float* k_b;
+    const float* v_w;
+    const float* v_b;
+    const float* c_w;
+    const float* c_b;
+    const reidmi_bottleneck_src* blocks;
+} reidmi_resnet_src;
+
+/* Packing in the manner of reidmi_vit_weights_pack: one caller-owned 256-byte aligned buffer of
+ * reidmi_resnet_pack_bytes (-1 on bad shapes: width % 64 != 0, a block count < 1, out_dim % 128
+ * != 0, more than 1024 tokens), stream-ordered; convolution weights re-laid to [Cout][kh][kw][Cin]
+ * and cast to fp16, BatchNorm reduced to (s, t) in fp64, the projections cast to fp16.
+ * out_blocks: HOST array of sum(layers) entries that out->blocks will point to (keep it alive). */
+int64_t reidmi_resnet_pack_bytes(const reidmi_resnet_src* src);
+int reidmi_resnet_weights_pack(const reidmi_resnet_src* src, void* buf, int64_t buf_bytes, reidmi_resnet_weights* out,
+                               reidmi_bottleneck_weights* out_blocks, void* stream);
+
+/* Workspace bytes of reidmi_resnet_forward for B images of H x Wimg; -1 for bad weights or an
+ * unsupported shape (H % 16, Wimg % 16, a grid other than the packed one, > 1024 tokens). */
+int64_t reidmi_resnet_workspace_bytes(const reidmi_resnet_weights* w, int64_t B, int H, int Wimg, int full);
+
+/* ModifiedResNet.forward (custom_clip_model.py:227-242) and what inference consumes of it
+ * (zero_shot_learning.py:88-90): images [B][3][H][Wimg] fp32 (images_f16 = 0) or fp16, already
+ * normalised; tta as for reidmi_vit_forward (flip + Pad((10,5)) + crop at (top, left), pad value
+ * w->tta_pad), materialised as an fp16 NHWC view in the workspace before the stem.
+ * full = 0: out_pool [B][32 w] = avg_pool2d(x4) over the whole map (fp32 mean of the fp16 x4),
+ *           out_proj [B][E] = attnpool(x4)[0].
+ * full = 1: the same out_pool, out_proj [L][B][E] (all L = H/16 * Wimg/16 + 1 tokens), and out_x3
+ *           [B][16 w][H/16][Wimg/16], out_x4 [B][32 w][H/16][Wimg/16] fp32 NCHW (each nullable).
+ * No allocation or synchronisation; ws_bytes >= reidmi_resnet_workspace_bytes is checked. */
+int reidmi_resnet_forward(const reidmi_resnet_weights* w, const void* images, int images_f16, int64_t B, int H,
+                          int Wimg, const int32_t* tta, int full, float* out_pool, float* out_proj, float* out_x3,
+                          float* out_x4, void* ws, int64_t ws_bytes, void* stream);
+
 /* -------------------------------------------------------- inference glue (G1) */
 
 /* zeroshot_classifier (zero_shot_learning.py:42-48): out[c] = normalize(mean over rows

@@ -82,6 +82,8 @@ SIGNATURES = {
     "reidmi_layernorm": [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _f32, _vp, _i64, _vp, _i64, _vp],
     "reidmi_row_stats_f16": [_vp, _i64, _i64, _i64, _vp, _vp, _vp],
     "reidmi_gemm_f16_resid_partials": [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp],
+    "reidmi_conv2d_f16": [_vp, _i64, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp],
+    "reidmi_avgpool2_f16": [_vp, _i64, _i32, _i32, _i32, _vp, _vp],
     "reidmi_feature_tta_avg": [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp],
     "reidmi_feature_tta_mm": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp],
     "reidmi_class_mean_normalize": [_vp, _vp, _i64, _i64, _vp, _vp],
@@ -122,10 +124,11 @@ TOOLS_SIGNATURES = {
     "reidmi_layernorm_f16": [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _f32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp],
     "reidmi_text_embed_f16": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _vp, _vp, _vp],
 }
-# entry points with struct arguments are typed in model.py (reidmi_vit_*, reidmi_text_*)
+# entry points with struct arguments are typed in model.py (reidmi_vit_*, reidmi_text_*, reidmi_resnet_*)
 STRUCT_ENTRY_POINTS = ("reidmi_vit_workspace_bytes", "reidmi_vit_forward", "reidmi_text_workspace_bytes",
                        "reidmi_text_forward", "reidmi_vit_pack_bytes", "reidmi_vit_weights_pack",
-                       "reidmi_text_pack_bytes", "reidmi_text_weights_pack")
+                       "reidmi_text_pack_bytes", "reidmi_text_weights_pack", "reidmi_resnet_pack_bytes",
+                       "reidmi_resnet_weights_pack", "reidmi_resnet_workspace_bytes", "reidmi_resnet_forward")
 
 _LIB = None
 _TOOLS = None

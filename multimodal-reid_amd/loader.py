@@ -274,9 +274,9 @@ def get_loader(dataset, batch_size, image_height, image_width, model_type, dtype
     the reference's order.  `tta_seed` seeds the augmented views' RandomCrop offsets (gallery
     and query draw from seeds tta_seed and tta_seed + 1).  `shard=(rank, world)`: each loader
     walks this rank's contiguous shard of its list (one process per GPU; the items keep the
-    offsets they have in one process) — feed the shards to get_cmc_map(..., sharded=True)."""
-    if model_type != "vit":
-        raise NotImplementedError("libreidmi implements the ViT tower (north-star path) only")
+    offsets they have in one process) — feed the shards to get_cmc_map(..., sharded=True).
+    `model_type` selects the normalisation statistics only (data_prepare.norm_stats: "vit" ->
+    0.5 / 0.5, anything else, e.g. "rn50" -> ImageNet's), as data_prepare.py:260,268."""
     g, ga = loader_pair(dataset.gallery, batch_size, image_height, image_width, model_type, dtype, device,
                         host_threads, depth, tta_seed, shard)
     q, qa = loader_pair(dataset.query, batch_size, image_height, image_width, model_type, dtype, device,

@@ -4,6 +4,8 @@ and the reference's model duck types.
     VisionTransformer.encode_image(img) -> (x11, x12, xproj)   custom_clip_model.py:77-100
                                                                maple.py:754-785 (IVLP, n_ctx>0)
     VisionTransformer.encode_cls(img, tta=None) -> (x12[:,0], xproj[:,0])  (inference fast path)
+    ModifiedResNet.encode_image(img) -> (x3, x4, xproj)        custom_clip_model.py:227-242
+    ModifiedResNet.encode_cls(img, tta=None) -> (avg_pool2d(x4), xproj[0])  (inference fast path)
     TextTransformer.encode_text(tokens) -> (N, E)              maple.py:971-984
     TextEncoder(text)(prompts, tokenized_prompts) -> (N, E)    text_encoder.py:14-24
     CLIP(visual, text): encode_image / encode_text / dtype      maple.py:964-984
@@ -65,7 +67,46 @@ class TextSrc(ctypes.Structure):  # reidmi_text_src
                                    "text_projection")] + [("blocks", ctypes.POINTER(BlockSrc))]
 
 
+class ConvWeights(ctypes.Structure):  # reidmi_conv_weights
+    _fields_ = [(n, _vp) for n in ("w", "scale", "shift")] + [(n, _i32) for n in ("cin", "cout", "k", "stride")]
+
+
+class BottleneckWeights(ctypes.Structure):  # reidmi_bottleneck_weights
+    _fields_ = [(n, ConvWeights) for n in ("conv1", "conv2", "conv3", "down")] + \
+               [(n, _i32) for n in ("stride", "has_down")]
+
+
+class ResnetWeights(ctypes.Structure):  # reidmi_resnet_weights
+    _fields_ = [(n, _i32) for n in ("width", "embed", "heads", "out_dim", "grid_h", "grid_w")] + \
+               [("layers", _i32 * 4), ("stem", ConvWeights * 3)] + \
+               [(n, _vp) for n in ("pos_emb", "qkv_w", "qkv_b", "c_w", "c_b")] + \
+               [("blocks", ctypes.POINTER(BottleneckWeights)), ("tta_pad", ctypes.c_float * 3)]
+
+
+class ConvBnSrc(ctypes.Structure):  # reidmi_convbn_src
+    _fields_ = [(n, _vp) for n in ("conv_w", "bn_w", "bn_b", "bn_mean", "bn_var")]
+
+
+class BottleneckSrc(ctypes.Structure):  # reidmi_bottleneck_src
+    _fields_ = [(n, ConvBnSrc) for n in ("conv1", "conv2", "conv3", "down")]
+
+
+class ResnetSrc(ctypes.Structure):  # reidmi_resnet_src
+    _fields_ = [(n, _i32) for n in ("width", "out_dim", "grid_h", "grid_w")] + \
+               [("layers", _i32 * 4), ("stem", ConvBnSrc * 3)] + \
+               [(n, _vp) for n in ("positional_embedding", "q_w", "q_b", "k_w", "k_b", "v_w", "v_b", "c_w", "c_b")] + \
+               [("blocks", ctypes.POINTER(BottleneckSrc))]
+
+
 _SIG = {
+    "reidmi_resnet_pack_bytes": ([ctypes.POINTER(ResnetSrc)], ctypes.c_int64),
+    "reidmi_resnet_weights_pack": ([ctypes.POINTER(ResnetSrc), _vp, ctypes.c_int64, ctypes.POINTER(ResnetWeights),
+                                    ctypes.POINTER(BottleneckWeights), _vp], ctypes.c_int),
+    "reidmi_resnet_workspace_bytes": ([ctypes.POINTER(ResnetWeights), ctypes.c_int64, ctypes.c_int, ctypes.c_int,
+                                       ctypes.c_int], ctypes.c_int64),
+    "reidmi_resnet_forward": ([ctypes.POINTER(ResnetWeights), _vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
+                               ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp],
+                              ctypes.c_int),
     "reidmi_vit_pack_bytes": ([ctypes.POINTER(VitSrc)], ctypes.c_int64),
     "reidmi_vit_weights_pack": ([ctypes.POINTER(VitSrc), _vp, ctypes.c_int64, ctypes.POINTER(VitWeights),
                                  ctypes.POINTER(BlockWeights), _vp], ctypes.c_int),
@@ -269,6 +310,138 @@ class VisionTransformer:
         xp = out_proj if out_proj is not None else torch.empty(B, self.out_dim, **kw)
         self._run(img, tta, False, x12, xp, None)
         return x12, xp
+
+
+def resnet_layers(sd):
+    """Block counts of layer1..4 read from the keys, as utils.py:237-238 does."""
+    return tuple(len({k.split(".")[1] for k in sd if k.startswith(f"layer{b}.")}) for b in (1, 2, 3, 4))
+
+
+def _convbn(sd, src, conv, bn):
+    c = ConvBnSrc()
+    c.conv_w = src.f32(sd[conv + ".weight"])
+    c.bn_w, c.bn_b = src.f32(sd[bn + ".weight"]), src.f32(sd[bn + ".bias"])
+    c.bn_mean, c.bn_var = src.f32(sd[bn + ".running_mean"]), src.f32(sd[bn + ".running_var"])
+    return c
+
+
+class ModifiedResNet:
+    """libreidmi ResNet image tower (custom_clip_model.ModifiedResNet, RN50 / RN101: stem width
+    64, layer4 at stride 1).  ``height`` / ``width_px`` are the input crop size (multiples of 16,
+    at most 1024 attention-pool tokens).  ``width`` is the pooled feature width 32 w (the
+    reference's attnpool.k_proj.in_features), ``out_dim`` the attention pool's output E, so that
+    zero_shot_learning.embed_pair serves both towers."""
+
+    def __init__(self, state_dict, height=256, width=128, device=None, prefix=""):
+        sd = {k[len(prefix):]: v for k, v in state_dict.items() if k.startswith(prefix)}
+        self.device = device or torch.device("cuda", torch.cuda.current_device())
+        w = int(_t(sd["layer1.0.conv1.weight"]).shape[0])
+        self.stem_width, self.layers = w, resnet_layers(sd)
+        self.width, self.heads = 32 * w, 32 * w // 64
+        self.out_dim = int(_t(sd["attnpool.c_proj.weight"]).shape[0])
+        self.height, self.img_width = height, width
+        gh, gw = height // 16, width // 16
+        self.grid = (gh, gw)
+        self.seq_len = 1 + gh * gw
+        pos = _t(sd["attnpool.positional_embedding"])
+        if pos.shape[0] != self.seq_len:
+            pos = resize_pos_embed(pos, gh, gw)  # utils.py:228-231
+        self.positional_embedding = pos
+        src = _Sources(self.device)
+        rs = ResnetSrc()
+        rs.width, rs.out_dim, rs.grid_h, rs.grid_w = w, self.out_dim, gh, gw
+        for i in range(4):
+            rs.layers[i] = self.layers[i]
+        for i in range(3):
+            rs.stem[i] = _convbn(sd, src, f"conv{i + 1}", f"bn{i + 1}")
+        nb = sum(self.layers)
+        bsrc = (BottleneckSrc * nb)()
+        bi = 0
+        for l, n in enumerate(self.layers):
+            for i in range(n):
+                p = f"layer{l + 1}.{i}."
+                for j in (1, 2, 3):
+                    setattr(bsrc[bi], f"conv{j}", _convbn(sd, src, p + f"conv{j}", p + f"bn{j}"))
+                if p + "downsample.0.weight" in sd:
+                    bsrc[bi].down = _convbn(sd, src, p + "downsample.0", p + "downsample.1")
+                bi += 1
+        rs.positional_embedding = src.f32(pos)
+        for n in "qkvc":
+            setattr(rs, n + "_w", src.f32(sd[f"attnpool.{n}_proj.weight"]))
+            setattr(rs, n + "_b", src.f32(sd[f"attnpool.{n}_proj.bias"]))
+        rs.blocks = bsrc
+        nbytes = _fn("reidmi_resnet_pack_bytes")(ctypes.byref(rs))
+        if nbytes < 0:
+            raise _lib.ReidmiError(f"reidmi_resnet_pack_bytes: {_lib.load().reidmi_last_error().decode()}")
+        self._packed = torch.empty(nbytes, dtype=torch.uint8, device=self.device)
+        self.weights = ResnetWeights()
+        self._blocks = (BottleneckWeights * nb)()
+        rc = _fn("reidmi_resnet_weights_pack")(ctypes.byref(rs), self._packed.data_ptr(), nbytes,
+                                               ctypes.byref(self.weights), self._blocks, _lib.stream(self.device))
+        if rc != 0:
+            raise _lib.ReidmiError(f"reidmi_resnet_weights_pack: {_lib.load().reidmi_last_error().decode()}")
+        del src
+        self._ws = {}
+
+    @property
+    def dtype(self):
+        return torch.float32
+
+    _images = VisionTransformer._images
+
+    def set_norm_stats(self, mean, std):
+        """The loader's Normalize statistics: a padded pixel of the TTA view is a zero pixel,
+        (0 - mean) / std after normalisation (-1 for the default 0.5 / 0.5)."""
+        for c in range(3):
+            self.weights.tta_pad[c] = (0.0 - float(mean[c])) / float(std[c])
+
+    def _run(self, img, tta, full, pool, proj, x3, x4):
+        img = self._images(img)
+        B, C, H, Wd = img.shape
+        if C != 3:
+            raise ValueError("expected (B,3,H,W) images")
+        nbytes = _fn("reidmi_resnet_workspace_bytes")(ctypes.byref(self.weights), B, H, Wd, int(full))
+        if nbytes < 0:
+            raise _lib.ReidmiError(_lib.load().reidmi_last_error().decode())
+        key = torch.cuda.current_stream(self.device).cuda_stream
+        ws = self._ws.get(key)
+        if ws is None or ws.numel() < nbytes:
+            self._ws.pop(key, None)
+            ws = torch.empty(max(nbytes, 1), dtype=torch.uint8, device=self.device)
+            self._ws[key] = ws
+        if tta is not None:
+            tta = torch.as_tensor(tta, dtype=torch.int32).to(self.device).contiguous()
+        rc = _fn("reidmi_resnet_forward")(ctypes.byref(self.weights), img.data_ptr(), int(img.dtype == torch.float16),
+                                          B, H, Wd, None if tta is None else tta.data_ptr(), int(full),
+                                          pool.data_ptr(), proj.data_ptr(), None if x3 is None else x3.data_ptr(),
+                                          None if x4 is None else x4.data_ptr(), ws.data_ptr(), nbytes,
+                                          _lib.stream(self.device))
+        if rc != 0:
+            raise _lib.ReidmiError(f"reidmi_resnet_forward: {_lib.load().reidmi_last_error().decode()}")
+
+    def encode_image(self, img):
+        """(x3 [B, 16w, H/16, W/16], x4 [B, 32w, H/16, W/16], xproj [HW+1, B, E]) fp32 —
+        custom_clip_model.py:242."""
+        B = img.shape[0]
+        gh, gw = self.grid
+        kw = dict(device=self.device, dtype=torch.float32)
+        x3, x4 = torch.empty(B, self.width // 2, gh, gw, **kw), torch.empty(B, self.width, gh, gw, **kw)
+        xp, pool = torch.empty(self.seq_len, B, self.out_dim, **kw), torch.empty(B, self.width, **kw)
+        self._run(img, None, True, pool, xp, x3, x4)
+        return x3, x4, xp
+
+    __call__ = encode_image
+
+    def encode_cls(self, img, tta=None, out_x12=None, out_proj=None):
+        """(avg_pool2d(x4) over the whole map, xproj[0]) of encode_image(img) (or of the augmented
+        view when ``tta`` [B,2] crop offsets are given) — what zero_shot_learning.py:88-90
+        consumes."""
+        B = img.shape[0]
+        kw = dict(device=self.device, dtype=torch.float32)
+        pool = out_x12 if out_x12 is not None else torch.empty(B, self.width, **kw)
+        xp = out_proj if out_proj is not None else torch.empty(B, self.out_dim, **kw)
+        self._run(img, tta, False, pool, xp, None, None)
+        return pool, xp
 
 
 class TextTransformer:

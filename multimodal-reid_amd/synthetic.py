@@ -23,6 +23,11 @@ VIT_SPECS = {
     "ViT-B/16": dict(width=768, layers=12, heads=12, patch=16, out_dim=512),
     "ViT-L/14": dict(width=1024, layers=24, heads=16, patch=14, out_dim=768),
 }
+# (block counts, stem width, out_dim) of the CLIP ResNet towers (custom_clip_model.ModifiedResNet)
+RESNET_SPECS = {
+    "RN50": dict(layers=(3, 4, 6, 3), width=64, out_dim=1024),
+    "RN101": dict(layers=(3, 4, 23, 3), width=64, out_dim=512),
+}
 TEXT_SPEC = dict(width=512, layers=12, heads=8, ctx=77, vocab=49408, out_dim=512)
 
 DATASET_SPLITS = {  # SURVEY.md §8d; sizes from datasets/*.py docstrings
@@ -91,6 +96,57 @@ def vit_state_dict(model="ViT-B/16", height=256, width=128, stride=12, seed=0, l
     sd["proj"] = _normal("proj", (w, E), scale, seed)
     if vpt_ctx:
         sd["VPT"] = _normal("VPT", (vpt_ctx, w), 0.02, seed)
+    return sd
+
+
+def _uniform(name, shape, lo, hi, seed):
+    return _rng(name, seed).uniform(lo, hi, shape).astype(np.float32)
+
+
+def resnet_state_dict(layers=(3, 4, 6, 3), width=64, out_dim=1024, height=256, width_px=128, seed=0):
+    """State dict (numpy) with the key layout of custom_clip_model.ModifiedResNet (strict=True
+    loadable: ``num_batches_tracked`` included), the attention pool on the height//16 x
+    width_px//16 grid.  He-scaled convolutions (std sqrt(2 / fan_in)); every BatchNorm has
+    ``weight`` and ``running_var`` in [0.5, 1.5] and ``bias`` / ``running_mean`` ~ N(0, 0.1), so
+    no statistic is trivial; the last BatchNorm of each block is scaled by 0.25, so the residual
+    sum of a 16- or 33-block tower stays O(1) in fp16."""
+    sd = {}
+
+    def conv(name, cout, cin, k):
+        sd[name + ".weight"] = _normal("rn." + name, (cout, cin, k, k), (2.0 / (cin * k * k)) ** 0.5, seed)
+
+    def bn(name, n, gain=1.0):
+        sd[name + ".weight"] = gain * _uniform("rn." + name + ".weight", (n,), 0.5, 1.5, seed)
+        sd[name + ".bias"] = _normal("rn." + name + ".bias", (n,), 0.1, seed)
+        sd[name + ".running_mean"] = _normal("rn." + name + ".running_mean", (n,), 0.1, seed)
+        sd[name + ".running_var"] = _uniform("rn." + name + ".running_var", (n,), 0.5, 1.5, seed)
+        sd[name + ".num_batches_tracked"] = np.array(100, np.int64)
+
+    w = width
+    for i, (cout, cin) in enumerate(((w // 2, 3), (w // 2, w // 2), (w, w // 2))):
+        conv(f"conv{i + 1}", cout, cin, 3)
+        bn(f"bn{i + 1}", cout)
+    inplanes = w
+    for l, n in enumerate(layers):
+        planes, stride = w << l, 2 if l in (1, 2) else 1
+        for i in range(n):
+            p = f"layer{l + 1}.{i}."
+            conv(p + "conv1", planes, inplanes, 1)
+            bn(p + "bn1", planes)
+            conv(p + "conv2", planes, planes, 3)
+            bn(p + "bn2", planes)
+            conv(p + "conv3", planes * 4, planes, 1)
+            bn(p + "bn3", planes * 4, gain=0.25)
+            if i == 0 and (stride > 1 or inplanes != planes * 4):
+                conv(p + "downsample.0", planes * 4, inplanes, 1)
+                bn(p + "downsample.1", planes * 4)
+            inplanes = planes * 4
+    C = 32 * w
+    L = (height // 16) * (width_px // 16) + 1
+    sd["attnpool.positional_embedding"] = _normal("rn.attnpool.positional_embedding", (L, C), C ** -0.5, seed)
+    for n, o in (("q", C), ("k", C), ("v", C), ("c", out_dim)):
+        sd[f"attnpool.{n}_proj.weight"] = _normal(f"rn.attnpool.{n}_proj.weight", (o, C), C ** -0.5, seed)
+        sd[f"attnpool.{n}_proj.bias"] = _normal(f"rn.attnpool.{n}_proj.bias", (o,), 0.02, seed)
     return sd
 
 
@@ -298,11 +354,21 @@ def clipreid_checkpoint(model="ViT-B/16", seed=0, height=256, width=128, stride=
     """CLIP-ReID checkpoint key layout that utils.model_adaptor reads (utils.py:184-221):
     ``image_encoder.*`` (the stride-12 vision tower), ``text_encoder.*`` (the text tower,
     zero_shot_learning.py:31-34) and the BNNeck ``bottleneck.*`` / ``bottleneck_proj.*``
-    BatchNorm1d buffers (utils.py:128-142)."""
-    vis = vit_state_dict(model, height=height, width=width, stride=stride, seed=seed, resid_gain=resid_gain)
+    BatchNorm1d buffers (utils.py:128-142).  ``model`` "RN50" / "RN101": the ResNet tower's keys
+    (resnet_state_dict; the reference reads its embed_dim from text_encoder.text_projection,
+    utils.py:239, which then has out_dim columns)."""
+    if model in RESNET_SPECS:
+        spec = RESNET_SPECS[model]
+        vis = resnet_state_dict(spec["layers"], spec["width"], spec["out_dim"], height, width, seed)
+        W, E = 32 * spec["width"], spec["out_dim"]
+    else:
+        vis = vit_state_dict(model, height=height, width=width, stride=stride, seed=seed, resid_gain=resid_gain)
+        W, E = VIT_SPECS[model]["width"], VIT_SPECS[model]["out_dim"]
     sd = {"image_encoder." + k: v for k, v in vis.items()}
     sd.update({"text_encoder." + k: v for k, v in text_state_dict(seed=seed).items()})
-    W, E = VIT_SPECS[model]["width"], VIT_SPECS[model]["out_dim"]
+    if model in RESNET_SPECS:
+        sd["text_encoder.text_projection"] = _normal("text_projection", (TEXT_SPEC["width"], E), TEXT_SPEC["width"] ** -0.5,
+                                                     seed)
     for name, n in (("bottleneck", W), ("bottleneck_proj", E)):
         sd[name + ".weight"] = _normal(name + ".weight", (n,), 0.05, seed, mean=1.0)
         sd[name + ".bias"] = np.zeros(n, np.float32)

@@ -19,7 +19,7 @@ BNNeck (utils.py:128-142) is constructed and loaded but, as in the reference's e
 import numpy as np
 import torch
 
-from .model import CLIP, TextTransformer, VisionTransformer, resize_pos_embed  # noqa: F401
+from .model import CLIP, ModifiedResNet, TextTransformer, VisionTransformer, resize_pos_embed  # noqa: F401
 
 
 def load_checkpoint(path):
@@ -53,18 +53,27 @@ class BNNeck:
 def model_adaptor(model, height, width, weights=None, model_type="vit", training_mode="coop",
                   vision_stride_size=12, device=None):
     """Build the libreidmi vision tower from a CLIP-ReID checkpoint (``image_encoder.*``
-    keys) exactly as utils.py:169-262 re-shapes the model: stride-12 patches, grid
-    height//12 x width//12, positional embedding bicubic-resized when its grid differs.
-    ``model`` may be None or a model.CLIP whose text tower is kept."""
-    if model_type != "vit":
-        raise NotImplementedError("libreidmi implements the ViT towers (north-star path)")
+    keys) exactly as utils.py:169-262 re-shapes the model.  ``model_type == "vit"``: stride-12
+    patches, grid height//12 x width//12.  Any other ``model_type`` (the reference's ``else``
+    branch, utils.py:225-260; e.g. "rn50"): custom_clip_model.ModifiedResNet with the block counts
+    and width read from the keys and the attention pool on the height//16 x width//16 grid
+    (``training_mode`` "coop" only).  The positional embedding is bicubic-resized when its grid
+    differs.  ``model`` may be None or a model.CLIP whose text tower is kept."""
     sd = load_checkpoint(weights) if isinstance(weights, str) else weights
     if sd is None:
         raise ValueError("model_adaptor: a checkpoint (path or state dict) is required")
     vis = {k[len("image_encoder."):]: v for k, v in sd.items() if k.startswith("image_encoder.")}
     if not vis:
         vis = {k[len("visual."):]: v for k, v in sd.items() if k.startswith("visual.")}
-    visual = VisionTransformer(vis, height=height, width=width, stride=vision_stride_size, device=device)
+    if model_type == "vit":
+        visual = VisionTransformer(vis, height=height, width=width, stride=vision_stride_size, device=device)
+    else:
+        if training_mode != "coop":
+            raise NotImplementedError("the ResNet tower exists in coop mode only (maple.ModifiedResNet is not built)")
+        if "layer1.0.conv1.weight" not in vis:
+            raise ValueError(f"model_adaptor: model_type {model_type!r} needs a ResNet checkpoint "
+                             "(image_encoder.layer1.0.conv1.weight is missing)")
+        visual = ModifiedResNet(vis, height=height, width=width, device=device)
     bottleneck = BNNeck(visual.width, False)
     bottleneck_proj = BNNeck(visual.out_dim, True)
     bneck = {k: v for k, v in sd.items() if "bottleneck" in k}

@@ -10,15 +10,18 @@
 Differences from the reference that do not change results: both TTA passes of a batch run
 back to back and the feature epilogue (average / concat / --mm softmax) is one HIP kernel;
 embeddings stay fp32 on the GPU (the reference keeps fp16 then copies to the CPU).
-``model`` is a model.CLIP / model.VisionTransformer (libreidmi).  Only model_type "vit"
-exists here (the north-star path is the ViT tower).
+``model`` is a model.CLIP / model.VisionTransformer / model.ModifiedResNet (libreidmi);
+model_type "vit" takes the CLS rows of the ViT tower, any other value the ResNet tower's
+avg_pool2d(x4) and xproj[0] (zero_shot_learning.py:88-90).
 """
 import numpy as np
 import torch
 
 from . import _lib
 from .evaluate import R1_mAP_eval
+from .data_prepare import norm_stats
 from .loader import TtaView
+from .model import ModifiedResNet
 
 
 def _vis(model):
@@ -55,9 +58,16 @@ def inference(model, bottleneck, bottleneck_proj, zeroshot_weights, loader, load
     """zero_shot_learning.py:61-134.  Loaders yield (images, target, cams, seqs, indices);
     the i-th batches of the two loaders hold the same images (shuffle=False).  An augmented
     batch may be a loader.TtaView (the device loaders of loader.get_loader): its flip / pad /
-    crop then run inside the encoder's im2col."""
-    if model_type != "vit":
-        raise NotImplementedError("libreidmi implements the ViT tower (north-star path) only")
+    crop then run inside the encoder.  ``model_type`` "vit" reads the ViT tower's CLS rows; any
+    other value is the reference's ``else`` branch (:88-90, :111-113), avg_pool2d(x4) and xproj[0]
+    of the ResNet tower: both arrive as encode_cls's pair, so the glue is shared.  A tower that
+    does not match ``model_type`` raises ValueError."""
+    vis = _vis(model)
+    if (model_type == "vit") == isinstance(vis, ModifiedResNet):
+        raise ValueError(f"inference: model_type {model_type!r} does not match the image tower "
+                         f"({type(vis).__name__})")
+    if model_type != "vit":  # the loaders' statistics (data_prepare.py:260,268) fix the TTA view's pad value
+        vis.set_norm_stats(*norm_stats(model_type))
     embeddings, targets, camera_ids, sequence_ids = [], [], [], []
     with torch.no_grad():
         for (images, target, cams, seqs, _), (images_aug, *_rest) in zip(loader, loader_augment):
