@@ -109,8 +109,39 @@ def test_conv2d_stem(gpu, H, W):
         _check(got, y64, abs64, s, t, r, relu, 27, f"stem {H}x{W} {name}")
 
 
+@pytest.mark.parametrize("cin,cout", [(32, 96), (64, 160)])
+@pytest.mark.parametrize("k", [1, 3])
+@pytest.mark.parametrize("H,W,stride", [(5, 3, 1), (14, 7, 1), (14, 7, 2)])
+def test_conv2d_32_wide_tiles_in_several_column_blocks(gpu, H, W, stride, k, cin, cout):
+    """Cout % 64 != 0 takes the 32-channel wave tile (conv_igemm_kernel<2>); with Cout > 32 it
+    runs in more than one column block (3 and 5 here), each at its own 32-channel offset."""
+    B = 3
+    g, a, w = _inputs(B, cin, cout, H, W, k, seed=H * 1000 + k * 100 + cout + stride)
+    y64 = F.conv2d(a.double(), w.double(), padding=k // 2, stride=stride)
+    abs64 = F.conv2d(a.double().abs(), w.double().abs(), padding=k // 2, stride=stride)
+    for name, s, t, r, relu in _variants(g, cout, y64.shape):
+        got = _conv(gpu, a, w, s, t, r, relu, k, stride)
+        _check(got, y64, abs64, s, t, r, relu, k * k * cin, f"{H}x{W} k{k}/{stride} {cin}->{cout} {name}")
+
+
+@pytest.mark.parametrize("H,W,stride,cout", [(7, 5, 2, 32), (9, 1, 2, 32),   # odd maps: the right and bottom taps
+                                             (7, 5, 1, 64),                  # stride 1
+                                             (6, 4, 2, 512), (6, 4, 1, 512)])  # the widest the kernel's LDS takes
+def test_conv2d_stem_odd_maps_stride_and_width(gpu, H, W, stride, cout):
+    """The 3-channel kernel away from the tower's own launch (even map, stride 2, 32 channels)."""
+    B = 3
+    g, a, w = _inputs(B, 3, cout, H, W, 3, seed=100 * H + 10 * W + stride)
+    y64 = F.conv2d(a.double(), w.double(), padding=1, stride=stride)
+    abs64 = F.conv2d(a.double().abs(), w.double().abs(), padding=1, stride=stride)
+    assert y64.shape == (B, cout, (H - 1) // stride + 1, (W - 1) // stride + 1)
+    for name, s, t, r, relu in _variants(g, cout, y64.shape):
+        got = _conv(gpu, a, w, s, t, r, relu, 3, stride)
+        _check(got, y64, abs64, s, t, r, relu, 27, f"stem {H}x{W}/{stride} 3->{cout} {name}")
+
+
 @pytest.mark.parametrize("k,cin,cout,H,W,stride", [(3, 64, 256, 5, 3, 1), (1, 256, 64, 14, 7, 1), (3, 32, 32, 16, 8, 2),
-                                                   (3, 3, 32, 32, 16, 2)])
+                                                   (3, 3, 32, 32, 16, 2),
+                                                   (3, 3, 32, 7, 5, 2)])   # the stem kernel on an odd map
 def test_conv2d_batch_independence(gpu, k, cin, cout, H, W, stride):
     """Image b of a B = 3 call equals the same image run alone, bit for bit: the padding never
     reads the neighbouring image and the per-element chain does not depend on the tile."""
@@ -122,10 +153,8 @@ def test_conv2d_batch_independence(gpu, k, cin, cout, H, W, stride):
         assert torch.equal(both[b:b + 1].view(torch.int16), one.view(torch.int16)), b
 
 
-@pytest.mark.parametrize("H,W", [(6, 4), (14, 8)])
-def test_avgpool2_bits(gpu, H, W):
+def _avgpool2_bits(gpu, B, H, W, C):
     from multimodal_reid_amd import _lib
-    B, C = 3, 32
     g = torch.Generator().manual_seed(H)
     # a wide exponent range, so that the fp32 sum does round and its order matters
     x = (torch.randn(B, H, W, C, generator=g) * torch.exp2(torch.randint(-12, 4, (B, H, W, C), generator=g).float())).half()
@@ -138,3 +167,14 @@ def test_avgpool2_bits(gpu, H, W):
     # and the mean itself: nn.AvgPool2d(2) in fp32 agrees to the last fp16 bit or the one next to it
     ref = F.avg_pool2d(f.permute(0, 3, 1, 2), 2).permute(0, 2, 3, 1)
     assert float((y.cpu().float() - ref).abs().max()) <= float((ref.abs() * 2.0 ** -10).max())
+
+
+@pytest.mark.parametrize("H,W", [(6, 4), (14, 8)])
+def test_avgpool2_bits(gpu, H, W):
+    _avgpool2_bits(gpu, 3, H, W, 32)
+
+
+@pytest.mark.parametrize("H,W,C", [(2, 2, 8),       # one output pixel, one thread per image
+                                   (4, 2, 2048)])   # the tower's widest map
+def test_avgpool2_bits_channel_edges(gpu, H, W, C):
+    _avgpool2_bits(gpu, 3, H, W, C)

@@ -84,6 +84,47 @@ def test_get_loader_inference_equals_embed_pair(gpu, vit, tmp_path):
         assert seqs.tolist() == [it[3] for it in items]
 
 
+def test_get_loader_inference_equals_embed_pair_rn50(gpu, tmp_path):
+    """The same with a ResNet tower and model_type="rn50": the loaders normalise with the ImageNet
+    statistics, inference() hands them to the tower as the TTA view's pad value, and the result
+    equals the per-call path bit for bit."""
+    from multimodal_reid_amd import data_prepare, loader, model
+    from multimodal_reid_amd import zero_shot_learning as zsl
+    H, W = 64, 32
+    vis = model.ModifiedResNet(syn.resnet_state_dict((1, 1, 1, 1), 64, 256, H, W, seed=0), H, W, device=gpu)
+    q_items, q_files = _items(40, 41, tmp_path)
+    g_items, g_files = _items(70, 42)
+    ds = types.SimpleNamespace(query=q_items, gallery=g_items)
+    lg, lq, lga, lqa = loader.get_loader(ds, 32, H, W, "rn50", tta_seed=7)
+    mean, std = data_prepare.norm_stats("rn50")
+    pad = [np.float32((0.0 - m) / s) for m, s in zip(mean, std)]
+    assert len(set(pad)) == 3
+    for lp, la, items, files, seed in ((lg, lga, g_items, g_files, 7), (lq, lqa, q_items, q_files, 8)):
+        offs = data_prepare.tta_offsets(len(files), seed)
+        seen = 0
+        for (im, *_l), (va, *_r) in zip(lp, la):
+            B = im.shape[0]
+            ref = data_prepare.preprocess_jpeg(files[seen:seen + B], H, W, model_type="rn50")
+            assert im.dtype == torch.float16 and torch.equal(im.view(torch.int16), ref.view(torch.int16))
+            assert isinstance(va, loader.TtaView) and va.images is im
+            assert np.array_equal(va.offsets.cpu().numpy(), offs[seen:seen + B])
+            seen += B
+        assert seen == len(files) and len(lp) == len(la) == (len(files) + 31) // 32
+        vis.set_norm_stats(*data_prepare.norm_stats("vit"))   # inference() has to set the pad itself
+        emb, tgt, cams, seqs = zsl.inference(model.CLIP(visual=vis), None, None, None, lp, la, False, "rn50")
+        assert [np.float32(vis.weights.tta_pad[c]) for c in range(3)] == pad
+        imgs = data_prepare.preprocess_jpeg(files, H, W, model_type="rn50")
+        vis.set_norm_stats(*data_prepare.norm_stats("rn50"))
+        ref = zsl.embed_pair(vis, imgs, tta=offs)
+        assert emb.shape == ref.shape == (len(files), vis.width + vis.out_dim)
+        assert torch.equal(emb.view(torch.int32), ref.view(torch.int32))
+        # (the pad value is part of that equality: with the ViT's -1 the rows differ)
+        vis.set_norm_stats(*data_prepare.norm_stats("vit"))
+        assert not torch.equal(zsl.embed_pair(vis, imgs, tta=offs).view(torch.int32), ref.view(torch.int32))
+        assert tgt.tolist() == [it[1] for it in items] and cams.tolist() == [it[2] for it in items]
+        assert seqs.tolist() == [it[3] for it in items]
+
+
 def test_loader_raises_on_undecodable_file(gpu):
     """No host fallback: a file the device cannot decode raises while iterating (as the
     reference's loader raises from PIL inside its workers)."""
