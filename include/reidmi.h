@@ -27,7 +27,8 @@ extern "C" {
 
 const char* reidmi_last_error(void);
 /* 4 since round 4: the A/B-only entry points (forced GEMM tiling, distance-kernel variant, the
- * fused QKV + attention kernel) moved to the tools library (include/reidmi_tools.h). */
+ * fused QKV + attention kernel) moved to the tools library (include/reidmi_tools.h).
+ * 5: reidmi_rr_jaccard_topk_rows / reidmi_rr_jaccard_topk_workspace_bytes added. */
 int reidmi_abi_version(void);
 
 /* ------------------------------------------------------------ retrieval back end */
@@ -249,6 +250,34 @@ int reidmi_rr_jaccard_rows(const float* feat, int64_t N, int64_t D, int64_t ldf,
                            const uint16_t* ival, uint16_t one_minus_lambda_h, float lambda_f, float* out, int64_t ldo,
                            float* chunk, int64_t chunk_rows, void* bounds, int64_t bounds_bytes, void* stream);
 int64_t reidmi_rr_jaccard_bounds_bytes(int64_t N, int64_t G);
+/* R6+R7 as ranked lists: for queries qlo..qhi, the k smallest entries of the rows that
+ * reidmi_rr_jaccard_rows would write, without those rows.  out_idx[(i-qlo)*ldo + 0..k) /
+ * out_dist[(i-qlo)*ldo + 0..k) (out_dist nullable) are, bit for bit, what reidmi_rr_jaccard_rows
+ * followed by reidmi_topk_rows_f32(k, row_div = NULL) gives on the same inputs: the same final
+ * distances (one definition of the per-element blend for both), ascending, ties by gallery index.
+ * The selection runs inside the Jaccard kernel, one sorted partial list per (query, 8192-column
+ * chunk); a small kernel merges a query's lists, so the result does not depend on the chunking.
+ * The inputs are reidmi_rr_jaccard_rows' (chunk: chunk_rows x G floats, 1 <= chunk_rows <= 65535;
+ * bounds as there).
+ * Labels: all four arrays or none; q_pids / q_cams are indexed by query row 0..Q, g_pids / g_cams
+ * by gallery item 0..G.  With labels, gallery item j is skipped for query i when g_pids[j] ==
+ * q_pids[i] && g_cams[j] == q_cams[i] (evaluate.py:46-48), and a row with fewer than k items left
+ * is padded with index -1 and distance +inf.
+ * 1 <= k <= min(G, 128); a larger k is refused (reidmi_rr_jaccard_rows + reidmi_topk_rows_f32 is
+ * the route).  Features must be finite.
+ * ws: reidmi_rr_jaccard_topk_workspace_bytes(chunk_rows, G, k) = chunk_rows * ceil(G / 8192) * k * 8
+ * bytes, 8-byte aligned: the partial lists of one row pass (no Q x G term; ws_bytes is checked;
+ * -1 for arguments the call refuses).  No allocation or synchronisation inside; every refusal
+ * happens before any HIP call and leaves its message in reidmi_last_error(). */
+int64_t reidmi_rr_jaccard_topk_workspace_bytes(int64_t rows_per_pass, int64_t G, int k);
+int reidmi_rr_jaccard_topk_rows(const float* feat, int64_t N, int64_t D, int64_t ldf, const float* sqn,
+                                const float* rowmax, int64_t Q, int64_t qlo, int64_t qhi, const int64_t* qoff,
+                                const int32_t* qcol, const uint16_t* qval, const int64_t* coff, const int32_t* irow,
+                                const uint16_t* ival, uint16_t one_minus_lambda_h, float lambda_f, int k,
+                                const int64_t* q_pids, const int64_t* q_cams, const int64_t* g_pids,
+                                const int64_t* g_cams, int32_t* out_idx, float* out_dist, int64_t ldo, float* chunk,
+                                int64_t chunk_rows, void* bounds, int64_t bounds_bytes, void* ws, int64_t ws_bytes,
+                                void* stream);
 /* Row utilities of the staged driver's exact-row fallback (reranking.HipStages): row maxima
  * skipping NaN (the od divisors, reranking.py:46); ordered compaction idx[0..*count) = positions
  * of the nonzero flags (np.nonzero; count: device int32); out[r] = x[row0 + idx[r]] (fp32 rows). */

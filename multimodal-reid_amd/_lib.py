@@ -69,6 +69,10 @@ SIGNATURES = {
     "reidmi_rr_jaccard_rows": [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
                                _u16, _f32, _vp, _i64, _vp, _i64, _vp, _i64, _vp],
     "reidmi_rr_jaccard_bounds_bytes": [_i64, _i64],
+    "reidmi_rr_jaccard_topk_workspace_bytes": [_i64, _i64, _i32],
+    "reidmi_rr_jaccard_topk_rows": [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
+                                    _u16, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp,
+                                    _i64, _vp],
     "reidmi_rowmax_f32": [_vp, _i64, _i64, _i64, _vp, _vp],
     "reidmi_nonzero_i32": [_vp, _i64, _vp, _vp, _vp],
     "reidmi_gather_rows_f32": [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp],

@@ -7,6 +7,8 @@
 //   R4 query expansion V_qe = mean of k2 rows    qe_kernel            (ELL, fp16)      reranking.py:73-78
 //   R5 inverted index                            csc_count/scan/fill(/sort) (CSC)      reranking.py:80-82
 //   R6+R7 Jaccard with sequential fp16 sums, blend with od, slice [:Q, Q:]  jaccard_kernel  reranking.py:84-100
+//         ... or, instead of the slice, its first k columns per row in   jaccard_kernel<true> + jaccard_merge_kernel
+//         stable argsort order (reidmi_rr_jaccard_topk_rows)
 // Two drivers: one-call (reidmi_rerank*: N x N distance materialised, capacity-sized ELL
 // rows) and staged (reidmi_rr_*: row ranges over exactly sized CSR buffers, distance rows
 // in chunks or recomputed, shardable over ranks; see multimodal_reid_amd/reranking.py).
@@ -18,6 +20,7 @@
 #include <algorithm>
 #include "backend.h"
 #include "gemm.h"
+#include "select.h"
 
 
 namespace reidmi {
@@ -43,8 +46,9 @@ constexpr int JCH = RR_JCH;   // gallery columns per Jaccard workgroup (fp16 acc
 // for bounds from rr_caps; a caller passing smaller scratch gets this instead of a fault)
 enum RrFlag : int { RR_SCRATCH = 8 };
 
-// smallest power of two >= max(n, 2): the padded length of a bitonic sort of n keys
-__host__ __device__ inline int pow2_ceil(int64_t n) {
+// smallest power of two >= max(n, 2): the padded length of a bitonic sort of n keys (select.h's
+// pow2_ceil starts at 1)
+__host__ __device__ inline int sort_len(int64_t n) {
     int64_t p = 2;
     while (p < n) p <<= 1;
     return (int)p;
@@ -88,11 +92,11 @@ static KrSlab kr_slab(int kf, int kh1) {
     const int64_t nb = (int64_t)kf * (kh1 + 1);
     int64_t o = 0;
     s.kr = o; o = align_up(o + (int64_t)kf * 4, 16);
-    s.krs = o; o = align_up(o + (int64_t)pow2_ceil(kf) * 4, 16);
+    s.krs = o; o = align_up(o + (int64_t)sort_len(kf) * 4, 16);
     s.ncnt = o; o = align_up(o + (int64_t)kf * 4, 16);
     s.acc = o; o = align_up(o + (int64_t)kf * 4, 16);
     s.cs = o; o = align_up(o + (int64_t)kf * kh1 * 4, 16);
-    s.lst = o; o = align_up(o + (int64_t)pow2_ceil(nb) * 4, 16);
+    s.lst = o; o = align_up(o + (int64_t)sort_len(nb) * 4, 16);
     s.w = o; o = align_up(o + nb * 4, 16);
     s.bytes = o;
     return s;
@@ -103,7 +107,7 @@ struct QeSlab {
 };
 static QeSlab qe_slab(int k2e, int64_t tcap) {
     QeSlab s{};
-    const int64_t P = pow2_ceil(tcap);
+    const int64_t P = sort_len(tcap);
     int64_t o = 0;
     s.soff = o; o = align_up(o + (int64_t)(k2e + 1) * 4, 16);
     s.scol = o; o = align_up(o + tcap * 4, 16);
@@ -177,13 +181,13 @@ __device__ float pairwise_f32(const float* a, int n) {
 }
 
 // The sorting network of every stage: the workgroup sorts k[0..n) ascending (keys below
-// 0x7fffffff) and, with PAYLOAD, moves v[t] along with k[t].  k and v hold pow2_ceil(n)
+// 0x7fffffff) and, with PAYLOAD, moves v[t] along with k[t].  k and v hold sort_len(n)
 // entries; the tail is padded here.  One barrier per pass, the first one after the padding, so
 // the caller's own writes of k[0..n) need none of their own.  Every thread of the workgroup
 // calls it.  Inlined, so that a caller's LDS arrays stay LDS accesses.
 template <bool PAYLOAD>
 __device__ __forceinline__ void bitonic_sort(int32_t* k, uint16_t* v, int n) {
-    const int P = pow2_ceil(n);
+    const int P = sort_len(n);
     for (int t = n + threadIdx.x; t < P; t += blockDim.x) k[t] = 0x7fffffff;
     __syncthreads();
     for (int kk = 2; kk <= P; kk <<= 1)
@@ -314,7 +318,7 @@ __device__ __forceinline__ bool row_has_all(const int32_t* R, int64_t ldr, int32
 
 // The end of a V row, from the expansion list lst[0..n) of item i to output row b
 // (reranking.py:66-71): np.unique, w = exp(-od[i, lst]), V[i, lst] = w / sum(w) in fp16.
-// lst holds pow2_ceil(n) ints and w n floats (LDS or the slab; inlined for either); wsum is
+// lst holds sort_len(n) ints and w n floats (LDS or the slab; inlined for either); wsum is
 // 4 ints of LDS.  Reached by all 256 threads; the row is complete when it returns.
 __device__ __forceinline__ void kr_finish_row(const DistSrc& ds, float dv, int64_t i, int64_t b, int32_t* lst, float* w,
                                               int n, int* wsum, int32_t* __restrict__ vcol,
@@ -755,7 +759,7 @@ __global__ void csc_fill_kernel(Rows V, int64_t N, const int64_t* __restrict__ o
 // rows are unique within a column, so any sort is the stable one.  Lists of up to
 // CSC_LDS entries are bitonic-sorted in LDS; longer ones (hub items in very large galleries)
 // in a power-of-two padded slice of a global scratch at 2 * off[c] (>= the padded length,
-// since pow2_ceil(len) < 2 len).
+// since sort_len(len) < 2 len).
 constexpr int CSC_LDS = 4096;
 
 __global__ __launch_bounds__(256) void csc_sort_kernel(const int64_t* __restrict__ off, int32_t* __restrict__ irow,
@@ -767,7 +771,7 @@ __global__ __launch_bounds__(256) void csc_sort_kernel(const int64_t* __restrict
     const int64_t b = off[c];
     const int n = (int)(off[c + 1] - b);
     if (n < 2) return;
-    const bool in_lds = pow2_ceil(n) <= CSC_LDS;
+    const bool in_lds = sort_len(n) <= CSC_LDS;
     int32_t* K = in_lds ? lk : sk + 2 * b;
     uint16_t* V = in_lds ? lv : sv + 2 * b;
     for (int t = threadIdx.x; t < n; t += blockDim.x) {
@@ -825,29 +829,56 @@ __global__ __launch_bounds__(256) void jaccard_bounds_kernel(const int64_t* __re
     cbnd[t] = lo;
 }
 
-// The epilogue of both Jaccard kernels for one (query, chunk): tmin[t] (fp16 bits in LDS) is
-// temp_min of chunk column t, od[t] its unscaled original distance, dv the query's od divisor.
-// Jaccard in fp16 (every op rounded, reranking.py:93), the blend in fp32 (reranking.py:95).
+// One final distance: tm = temp_min's fp16 bits, od the unscaled original distance, dv the query's
+// od divisor, lam = fp32 of the fp16 (1 - lambda).  Jaccard in fp16 (every op rounded,
+// reranking.py:93), the blend in fp32 (reranking.py:95).  The one definition for every Jaccard
+// kernel, matrix or selecting form.
+__device__ __forceinline__ float jaccard_blend_one(uint16_t tm, float od, float dv, float lam, float lam_f) {
+    const float tv = h2f_bits(tm);
+    const uint16_t den = f2h_bits(2.0f - tv);
+    const uint16_t qt = f2h_bits(tv / h2f_bits(den));
+    const uint16_t jac = f2h_bits(1.0f - h2f_bits(qt));
+    const float a = h2f_bits(f2h_bits(h2f_bits(jac) * lam));
+    const float b = (od / dv) * lam_f;
+    return a + b;
+}
+
+// The epilogue of the matrix forms for one (query, chunk): tmin[t] (fp16 bits in LDS) is temp_min
+// of chunk column t, od[t] its unscaled original distance.
 __device__ __forceinline__ void jaccard_blend(const uint16_t* tmin, int span, const float* __restrict__ od, float dv,
                                               uint16_t lam16, float lam_f, float* __restrict__ out) {
     const float lam = h2f_bits(lam16);
-    for (int t = threadIdx.x; t < span; t += blockDim.x) {
-        const float tv = h2f_bits(tmin[t]);
-        const uint16_t den = f2h_bits(2.0f - tv);
-        const uint16_t qt = f2h_bits(tv / h2f_bits(den));
-        const uint16_t jac = f2h_bits(1.0f - h2f_bits(qt));
-        const float a = h2f_bits(f2h_bits(h2f_bits(jac) * lam));
-        const float b = (od[t] / dv) * lam_f;
-        out[t] = a + b;
-    }
+    for (int t = threadIdx.x; t < span; t += blockDim.x) out[t] = jaccard_blend_one(tmin[t], od[t], dv, lam, lam_f);
 }
 
+// jaccard_kernel<false> is the matrix form above.  jaccard_kernel<true> is the selecting form
+// (reidmi_rr_jaccard_topk_rows): the same walk and the same per-element blend, but the chunk's
+// final distances are never stored (out / ldo unused).  The workgroup selects the K smallest
+// (value, gallery index) of its chunk (topk_row_dev; within a chunk the order by chunk column is
+// the order by gallery index) among the columns the label predicate keeps (evaluate.py:46-48:
+// not the query's own pid and camera), and writes them as a sorted partial list
+// part[(blockIdx.y * chunks + chunk) * K + 0..K), padded with (+inf, -1); entries carry the
+// gallery index.  jaccard_merge_kernel joins a query's lists.  LDS: the matrix form's 20 KB +
+// TkLds = 36.9 KB, four workgroups per CU (the matrix form: eight).
+// The selecting form's extra arguments: the list length, the label arrays (all null: every column
+// is kept) and the partial lists.  The matrix form's are empty, and last, so that its
+// instantiation compiles to the code it had as a plain kernel.
+template <bool SELECT>
+struct JcSelect {};
+template <>
+struct JcSelect<true> {
+    int K;
+    const int64_t *qp, *qc, *gp, *gc;
+    float2* part;
+};
+
+template <bool SELECT>
 __global__ __launch_bounds__(256) void jaccard_kernel(const float* __restrict__ OD, int64_t ld, int64_t odc0,
                                                       const float* __restrict__ rowdiv, int64_t q0, int64_t Q,
                                                       int64_t N, Rows Vq, const int64_t* __restrict__ off,
                                                       const int32_t* __restrict__ irow, const uint16_t* __restrict__ ival,
                                                       const int64_t* __restrict__ cbnd, uint16_t lam16, float lam_f,
-                                                      float* __restrict__ out, int64_t ldo) {
+                                                      float* __restrict__ out, int64_t ldo, JcSelect<SELECT> sel) {
     __shared__ uint16_t tmin[JCH];
     const int64_t y = blockIdx.y;
     const int64_t i = q0 + y;
@@ -906,7 +937,38 @@ __global__ __launch_bounds__(256) void jaccard_kernel(const float* __restrict__ 
             __syncthreads();
         }
     }
-    jaccard_blend(tmin, span, OD + y * ld + (base - odc0), rowdiv[i], lam16, lam_f, out + y * ldo + (base - Q));
+    if constexpr (!SELECT) {
+        jaccard_blend(tmin, span, OD + y * ld + (base - odc0), rowdiv[i], lam16, lam_f, out + y * ldo + (base - Q));
+    } else {
+        __shared__ TkLds L;
+        const float* __restrict__ od = OD + y * ld + (base - odc0);
+        const float dv = rowdiv[i], lam = h2f_bits(lam16);
+        const int64_t g0 = base - Q;  // gallery index of chunk column 0
+        auto val = [&](int64_t t) { return jaccard_blend_one(tmin[t], od[t], dv, lam, lam_f); };
+        if (sel.qp) {
+            const int64_t qp = sel.qp[i], qc = sel.qc[i];
+            topk_row_dev(val, span, sel.K, L,
+                         [&](float, int t) { return !(sel.gp[g0 + t] == qp && sel.gc[g0 + t] == qc); });
+        } else {
+            topk_row_dev(val, span, sel.K, L);
+        }
+        const int n = L.s_nsel;
+        float2* __restrict__ dst = sel.part + (y * gridDim.x + blockIdx.x) * (int64_t)sel.K;
+        for (int t = threadIdx.x; t < sel.K; t += blockDim.x)
+            dst[t] = t < n ? make_float2(L.sv[t], __int_as_float((int)(g0 + L.si[t])))
+                           : make_float2(__builtin_inff(), __int_as_float(-1));
+    }
+}
+
+// One workgroup per query row of the pass: joins the row's `chunks` partial lists (topk_merge_dev).
+__global__ __launch_bounds__(256) void jaccard_merge_kernel(const float2* __restrict__ part, int chunks, int K,
+                                                            int32_t* __restrict__ out_idx,
+                                                            float* __restrict__ out_dist, int64_t ldo) {
+    __shared__ TkLds L;
+    const int64_t y = blockIdx.x;
+    const float2* __restrict__ mine = part + y * chunks * (int64_t)K;
+    topk_merge_dev([&](int64_t p) { return mine[p]; }, (int64_t)chunks * K, K, L, out_idx + y * ldo,
+                   out_dist ? out_dist + y * ldo : nullptr);
 }
 
 // ---------------------------------------------------------------- workspace
@@ -1798,8 +1860,77 @@ REIDMI_API int reidmi_rr_jaccard_rows(const float* feat, int64_t N, int64_t D, i
         if ((rc = distmat_pre_launch(feat + a * ldf, nb, ldf, feat + Q * ldf, G, ldf, D, sqn + a, sqn + Q, chunk, G, s)))
             return rc;
         dim3 grid(ceil_div(G, JCH), (unsigned)nb);
-        hipLaunchKernelGGL(jaccard_kernel, grid, dim3(256), 0, s, (const float*)chunk, G, Q, rowmax, a, Q, N, Vq, coff,
-                           irow, ival, (const int64_t*)cbnd, one_minus_lambda_h, lambda_f, out + (a - qlo) * ldo, ldo);
+        hipLaunchKernelGGL(jaccard_kernel<false>, grid, dim3(256), 0, s, (const float*)chunk, G, Q, rowmax, a, Q, N, Vq,
+                           coff, irow, ival, (const int64_t*)cbnd, one_minus_lambda_h, lambda_f, out + (a - qlo) * ldo,
+                           ldo, JcSelect<false>{});
+        RM_LAUNCHED();
+    }
+    return OK;
+}
+
+// Partial lists of one row pass of reidmi_rr_jaccard_topk_rows: k (value, index) pairs per
+// (query row of the pass, chunk).  -1 on arguments the call itself refuses.
+constexpr int JT_K_MAX = 128;
+static int64_t jaccard_topk_ws_bytes(int64_t rows, int64_t G, int k) {
+    if (rows < 1 || rows > 65535 || G < 1 || G >= 0x7fffffff || k < 1 || k > JT_K_MAX || k > G) return -1;
+    return rows * ((G + JCH - 1) / JCH) * k * 8;
+}
+
+REIDMI_API int64_t reidmi_rr_jaccard_topk_workspace_bytes(int64_t rows_per_pass, int64_t G, int k) {
+    return jaccard_topk_ws_bytes(rows_per_pass, G, k);
+}
+
+// reidmi_rr_jaccard_rows with the selection in the Jaccard kernel: per row pass, the chunk's od
+// rows, one sorted partial list per (query, chunk) (jaccard_kernel<true>), one merge per query
+// (jaccard_merge_kernel).  The passes reuse ws in stream order.
+REIDMI_API int reidmi_rr_jaccard_topk_rows(const float* feat, int64_t N, int64_t D, int64_t ldf, const float* sqn,
+                                           const float* rowmax, int64_t Q, int64_t qlo, int64_t qhi,
+                                           const int64_t* qoff, const int32_t* qcol, const uint16_t* qval,
+                                           const int64_t* coff, const int32_t* irow, const uint16_t* ival,
+                                           uint16_t one_minus_lambda_h, float lambda_f, int k, const int64_t* q_pids,
+                                           const int64_t* q_cams, const int64_t* g_pids, const int64_t* g_cams,
+                                           int32_t* out_idx, float* out_dist, int64_t ldo, float* chunk,
+                                           int64_t chunk_rows, void* bounds, int64_t bounds_bytes, void* ws,
+                                           int64_t ws_bytes, void* stream) {
+    const int64_t G = N - Q;
+    RM_REQUIRE(N > 0 && D > 0 && ldf >= D && 0 <= qlo && qlo <= qhi && qhi <= Q && Q <= N && G < 0x7fffffff,
+               "rr_jaccard_topk_rows: bad shape or row range");
+    RM_REQUIRE(k >= 1 && k <= G, "rr_jaccard_topk_rows: need 1 <= k <= G");
+    RM_REQUIRE(k <= JT_K_MAX,
+               "rr_jaccard_topk_rows: k > 128 is not fused; use reidmi_rr_jaccard_rows + reidmi_topk_rows_f32 for "
+               "larger k");
+    RM_REQUIRE(out_idx != nullptr && ldo >= k, "rr_jaccard_topk_rows: out_idx required, ldo >= k");
+    const int nlab = (q_pids != nullptr) + (q_cams != nullptr) + (g_pids != nullptr) + (g_cams != nullptr);
+    RM_REQUIRE(nlab == 0 || nlab == 4, "rr_jaccard_topk_rows: pass all four label arrays or none");
+    RM_REQUIRE(chunk_rows > 0 && chunk_rows <= 65535, "rr_jaccard_topk_rows: need 1 <= chunk_rows <= 65535");
+    RM_REQUIRE(ws != nullptr && ((uintptr_t)ws & 7) == 0 && ws_bytes >= jaccard_topk_ws_bytes(chunk_rows, G, k),
+               "rr_jaccard_topk_rows: workspace (reidmi_rr_jaccard_topk_workspace_bytes(chunk_rows, N-Q, k), 8-byte "
+               "aligned) required");
+    RM_REQUIRE(bounds && ((uintptr_t)bounds & 7) == 0 && bounds_bytes >= jaccard_bounds_bytes(N, G),
+               "rr_jaccard_topk_rows: bounds of reidmi_rr_jaccard_bounds_bytes(N, N-Q) bytes (8-byte aligned) required");
+    if (qhi == qlo) return OK;
+    RM_REQUIRE(feat && sqn && rowmax && qoff && coff && chunk, "rr_jaccard_topk_rows: inputs required");
+    hipStream_t s = (hipStream_t)stream;
+    const Rows Vq = csr_rows(qoff, qcol, qval);
+    const int nch = ceil_div(G, JCH);
+    int64_t* cbnd = (int64_t*)bounds;
+    hipLaunchKernelGGL(jaccard_bounds_kernel, dim3(ceil_div(N * (nch + 1), 256)), dim3(256), 0, s, coff, irow, N, Q,
+                       nch, cbnd);
+    RM_LAUNCHED();
+    const JcSelect<true> sel{k, q_pids, q_cams, g_pids, g_cams, (float2*)ws};
+    const float2* part = sel.part;
+    int rc;
+    for (int64_t a = qlo; a < qhi; a += chunk_rows) {
+        const int64_t nb = qhi - a < chunk_rows ? qhi - a : chunk_rows;
+        // original_dist[a:a+nb, Q:N] (chunk, ld G)
+        if ((rc = distmat_pre_launch(feat + a * ldf, nb, ldf, feat + Q * ldf, G, ldf, D, sqn + a, sqn + Q, chunk, G, s)))
+            return rc;
+        hipLaunchKernelGGL(jaccard_kernel<true>, dim3(nch, (unsigned)nb), dim3(256), 0, s, (const float*)chunk, G, Q,
+                           rowmax, a, Q, N, Vq, coff, irow, ival, (const int64_t*)cbnd, one_minus_lambda_h, lambda_f,
+                           (float*)nullptr, (int64_t)0, sel);
+        RM_LAUNCHED();
+        hipLaunchKernelGGL(jaccard_merge_kernel, dim3((unsigned)nb), dim3(256), 0, s, part, nch, k,
+                           out_idx + (a - qlo) * ldo, out_dist ? out_dist + (a - qlo) * ldo : nullptr, ldo);
         RM_LAUNCHED();
     }
     return OK;

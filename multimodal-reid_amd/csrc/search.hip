@@ -93,8 +93,6 @@ struct SrLabels {
     const int64_t *qp, *qc, *gp, *gc;
 };
 
-__device__ __forceinline__ int sr_idx(float2 e) { return __float_as_int(e.y); }
-
 // One wave compacts one row: list[0, n) -> the min(n, K) smallest in ascending (v, j) order.
 __device__ __forceinline__ void sr_compact_row(float2* __restrict__ list, uint64_t* sc, int n, int K, bool last,
                                                float* tv, int* ti, int* cnt, int lane) {
@@ -104,7 +102,7 @@ __device__ __forceinline__ void sr_compact_row(float2* __restrict__ list, uint64
         const float2 e = list[t];
         uint32_t u = __float_as_uint(e.x);
         u ^= (u >> 31) ? 0xffffffffu : 0x80000000u;
-        sc[t] = ((uint64_t)u << 32) | (uint32_t)sr_idx(e);
+        sc[t] = ((uint64_t)u << 32) | (uint32_t)kv_idx(e);
     }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();
@@ -286,21 +284,15 @@ __global__ __launch_bounds__(256, DM2_MINWG) void search_f32_kernel(
     }
 }
 
-// Joins the S partial lists of one row (each sorted by (v, j), ranges ascending in j, so the order
-// by (v, position in the concatenation) is the order by (v, j)); padding entries are skipped.
+// Joins the S partial lists of one row (each sorted by (v, j), ranges ascending in j: select.h
+// topk_merge_dev).
 __global__ __launch_bounds__(256) void search_merge_kernel(const float2* __restrict__ lists, int64_t bands, int S,
                                                            int cap, int K, int32_t* __restrict__ out_idx,
                                                            float* __restrict__ out_dist, int64_t ldo) {
     __shared__ TkLds L;
     const int64_t row = blockIdx.x, band = row / DM_BM, r = row % DM_BM;
     auto at = [&](int64_t p) { return lists[(((p / K) * bands + band) * DM_BM + r) * (int64_t)cap + p % K]; };
-    topk_row_dev([&](int64_t p) { return at(p).x; }, (int64_t)S * K, K, L,
-                 [&](float, int p) { return sr_idx(at(p)) >= 0; });
-    const int n = L.s_nsel;
-    for (int t = threadIdx.x; t < K; t += blockDim.x) {
-        out_idx[row * ldo + t] = t < n ? sr_idx(at(L.si[t])) : -1;
-        if (out_dist) out_dist[row * ldo + t] = t < n ? L.sv[t] : __builtin_inff();
-    }
+    topk_merge_dev(at, (int64_t)S * K, K, L, out_idx + row * ldo, out_dist ? out_dist + row * ldo : nullptr);
 }
 
 // The launcher's choices, pure functions of the arguments: S gallery ranges of range_len columns

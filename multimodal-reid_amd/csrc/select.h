@@ -96,4 +96,24 @@ __device__ inline void topk_row_dev(VAL val, int64_t cols, int K, TkLds& L, KEEP
     }
 }
 
+// ------------------------------------------------------------- partial lists
+// A partial list entry is a float2 (value, the index's bits); padding is (+inf, -1).
+__device__ __forceinline__ int kv_idx(float2 e) { return __float_as_int(e.y); }
+
+// Joins the partial lists of one row by the whole workgroup: at(p), p < total, is entry p of
+// their concatenation.  Each list is sorted by (value, index) and the lists cover ascending
+// index ranges, so the order by (value, position) is the order by (value, index); padding
+// entries are skipped.  out_idx / out_dist (nullable) [K] get the K smallest, a short result
+// padded with -1 / +inf.
+template <typename AT>
+__device__ inline void topk_merge_dev(AT at, int64_t total, int K, TkLds& L, int32_t* __restrict__ out_idx,
+                                      float* __restrict__ out_dist) {
+    topk_row_dev([&](int64_t p) { return at(p).x; }, total, K, L, [&](float, int p) { return kv_idx(at(p)) >= 0; });
+    const int n = L.s_nsel;
+    for (int t = threadIdx.x; t < K; t += blockDim.x) {
+        out_idx[t] = t < n ? kv_idx(at(L.si[t])) : -1;
+        if (out_dist) out_dist[t] = t < n ? L.sv[t] : __builtin_inff();
+    }
+}
+
 }  // namespace reidmi

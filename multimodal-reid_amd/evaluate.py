@@ -257,8 +257,11 @@ class R1_mAP_eval():
         output"): numpy (idx int32 [num_query][k], dist fp32 [num_query][k]) of the query rows against
         the gallery rows, features normalised as compute() does, nearest first, ties by gallery index;
         with remove_same_cam the gallery items of the query's pid and camera are left out
-        (evaluate.py:46-48; short rows end in -1 / +inf).  Single-process semantics on this process's
-        data (no re-ranked or sharded form)."""
+        (evaluate.py:46-48; short rows end in -1 / +inf).  With ``reranking=True`` the lists are those
+        of the k-reciprocal re-ranked distance compute() scores (k1 = 50, k2 = 15, lambda = 0.3;
+        reranking.re_ranking_search, no (Q, G) matrix), dist the re-ranked distances; otherwise the
+        Euclidean neighbours (search).  1 <= k <= min(num_gallery, 128).  Single-process semantics on
+        this process's data (no sharded form)."""
         from . import distributed as rd
         feats = torch.cat(self.feats, dim=0)
         if self.feat_norm:
@@ -269,6 +272,9 @@ class R1_mAP_eval():
             lab = (np.asarray(self.pids[:nq]), np.asarray(self.camids[:nq]), np.asarray(self.pids[nq:]),
                    np.asarray(self.camids[nq:]))
         with rd.local():
+            if self.reranking:
+                from .reranking import re_ranking_search
+                return re_ranking_search(feats[:nq], feats[nq:], k, 50, 15, 0.3, *lab)
             return search(feats[:nq], feats[nq:], k, *lab)
 
     @staticmethod

@@ -450,31 +450,67 @@ class HipStages:
             parts.append((cnt, qcol, qval))
         return self._cat(parts)
 
-    def jaccard_rows(self, rmax, Vq, qlo, qhi):
+    def _csc(self, Vq):
+        """R5: the inverted index of V_qe (coff, irow, ival), rows ascending per column."""
         off, col, val = Vq
-        N, Q = self.N, self.Q
-        G = N - Q
+        N = self.N
         nnz = int(off[-1].item())
-        L = _lib.load()
-        wsb = L.reidmi_rr_csc_workspace_bytes(N, nnz)
+        wsb = _lib.load().reidmi_rr_csc_workspace_bytes(N, nnz)
         ws = torch.empty(max(wsb, 1), device=self.dev, dtype=torch.uint8)
         coff = torch.empty(N + 1, device=self.dev, dtype=torch.int64)
         irow = torch.empty(max(nnz, 1), device=self.dev, dtype=torch.int32)
         ival = torch.empty(max(nnz, 1), device=self.dev, dtype=torch.int16)
         _lib.call("reidmi_rr_csc", N, _lib.ptr(off), _lib.ptr(col), _lib.ptr(val), nnz, _lib.ptr(coff), _lib.ptr(irow),
                   _lib.ptr(ival), _lib.ptr(ws), wsb, self.st)
-        del ws
+        return coff, irow, ival
+
+    def _jaccard_pass(self, qlo, qhi):
+        """(bounds scratch, its bytes, query rows per pass) of the R6 + R7 calls."""
+        N, G = self.N, self.N - self.Q
+        bb = int(_lib.load().reidmi_rr_jaccard_bounds_bytes(N, G))
+        bounds = torch.empty((bb + 7) // 8, device=self.dev, dtype=torch.int64)
+        cr = int(max(1, min(65535, qhi - qlo, self.chunk_rows * N // max(G, 1))))
+        return bounds, bb, cr
+
+    def jaccard_rows(self, rmax, Vq, qlo, qhi):
+        off, col, val = Vq
+        N, Q = self.N, self.Q
+        G = N - Q
+        coff, irow, ival = self._csc(Vq)
         out = torch.empty((qhi - qlo, G), device=self.dev, dtype=torch.float32)
         if qhi > qlo and G > 0:
-            L = _lib.load()
-            bb = int(L.reidmi_rr_jaccard_bounds_bytes(N, G))
-            bounds = torch.empty((bb + 7) // 8, device=self.dev, dtype=torch.int64)
-            cr = int(max(1, min(65535, qhi - qlo, self.chunk_rows * N // max(G, 1))))
+            bounds, bb, cr = self._jaccard_pass(qlo, qhi)
             _lib.call("reidmi_rr_jaccard_rows", _lib.ptr(self.feat), N, self.D, self.D, _lib.ptr(self.sqn),
                       _lib.ptr(rmax), Q, qlo, qhi, _lib.ptr(off), _lib.ptr(col), _lib.ptr(val), _lib.ptr(coff),
                       _lib.ptr(irow), _lib.ptr(ival), self.lam_h, self.lam_f, _lib.ptr(out), G,
                       _lib.ptr(self._chunk_buf(cr, G)), cr, _lib.ptr(bounds), bb, self.st)
         return out
+
+    def jaccard_topk_rows(self, rmax, Vq, qlo, qhi, k, labels=None, with_dist=True):
+        """R5-R7 as ranked lists (reidmi_rr_jaccard_topk_rows): (idx int32 [qhi-qlo][k], dist fp32 or
+        None) = the first k columns of jaccard_rows' rows in stable argsort order, selected inside
+        the Jaccard kernel; the (qhi-qlo, G) rows are never written.  labels: (q_pids, q_camids,
+        g_pids, g_camids) device int64 over all Q queries / G gallery items, or None."""
+        off, col, val = Vq
+        N, Q = self.N, self.Q
+        G = N - Q
+        k = int(k)
+        check_topk(G, k)
+        idx = torch.empty((qhi - qlo, k), device=self.dev, dtype=torch.int32)
+        dist = torch.empty((qhi - qlo, k), device=self.dev, dtype=torch.float32) if with_dist else None
+        if qhi == qlo:  # (a rank without query rows)
+            return idx, dist
+        qp, qc, gp, gc = labels if labels is not None else (None,) * 4
+        coff, irow, ival = self._csc(Vq)
+        bounds, bb, cr = self._jaccard_pass(qlo, qhi)
+        wsb = int(_lib.load().reidmi_rr_jaccard_topk_workspace_bytes(cr, G, k))
+        ws = torch.empty(wsb // 8, device=self.dev, dtype=torch.int64)  # one pass's partial lists
+        _lib.call("reidmi_rr_jaccard_topk_rows", _lib.ptr(self.feat), N, self.D, self.D, _lib.ptr(self.sqn),
+                  _lib.ptr(rmax), Q, qlo, qhi, _lib.ptr(off), _lib.ptr(col), _lib.ptr(val), _lib.ptr(coff),
+                  _lib.ptr(irow), _lib.ptr(ival), self.lam_h, self.lam_f, k, _lib.ptr(qp), _lib.ptr(qc), _lib.ptr(gp),
+                  _lib.ptr(gc), _lib.ptr(idx), _lib.ptr(dist), k, _lib.ptr(self._chunk_buf(cr, G)), cr,
+                  _lib.ptr(bounds), bb, _lib.ptr(ws), wsb, self.st)
+        return idx, dist
 
     def check(self):
         _check(self.flags)
@@ -488,9 +524,18 @@ def _gather_csr(stages, nnz_loc, col_loc, val_loc, N):
     return stages.offsets(nnz), col, val
 
 
-def staged_rerank(stages, N, Q):
+def check_topk(G, k):
+    """The list length reidmi_rr_jaccard_topk_rows accepts, refused here before any stage runs."""
+    if _lib.load().reidmi_rr_jaccard_topk_workspace_bytes(1, G, int(k)) < 0:
+        raise _lib.ReidmiError(f"re-ranked search: need 1 <= k <= min(G, 128) (k = {k}, G = {G}); for a larger k "
+                               "take re_ranking_device + topk_rows_device")
+
+
+def staged_rerank(stages, N, Q, topk=None, labels=None, with_dist=True):
     """R1-R7 over this rank's rows (torch.distributed world; world 1 = the whole job).
-    Returns this rank's rows shard(Q, rank, W) of the final (Q, G) distance."""
+    Returns this rank's rows shard(Q, rank, W) of the final (Q, G) distance; with ``topk`` = k,
+    those rows' ranked lists instead (idx int32 [rows][k], dist fp32 or None), the matrix rows
+    never written (HipStages.jaccard_topk_rows; labels as there)."""
     from . import distributed as rd
     rank, W = rd.world()
     lo, hi = rd.shard(N, rank, W)
@@ -505,9 +550,65 @@ def staged_rerank(stages, N, Q):
     else:
         Vq = V
     qlo, qhi = rd.shard(Q, rank, W)
-    out = stages.jaccard_rows(rmax, Vq, qlo, qhi)                 # R5-R7 (reranking.py:80-100)
+    if topk is not None:
+        out = stages.jaccard_topk_rows(rmax, Vq, qlo, qhi, topk, labels, with_dist)
+    else:
+        out = stages.jaccard_rows(rmax, Vq, qlo, qhi)             # R5-R7 (reranking.py:80-100)
     stages.check()
     return out
+
+
+def re_ranking_search_device(probFea, galFea, k, k1, k2, lambda_value, q_pids=None, q_camids=None, g_pids=None,
+                             g_camids=None, with_dist=True, sharded=False, chunk_bytes=None, local_distmat=None,
+                             only_local=False):
+    """The k best gallery items of every query under the re-ranked distance, without the (Q, G)
+    matrix: (idx int32 [Q][k], dist fp32 [Q][k] or None) on the GPU, bit for bit
+    re_ranking_device + topk_rows_device (ascending, ties by gallery index).  The staged stages
+    run at any size (bit-identical to the one-call path); the last one selects inside the Jaccard
+    kernel (reidmi_rr_jaccard_topk_rows).  With the four label arrays, gallery items of the query's
+    pid and camera are skipped (evaluate.py:46-48) and short rows are padded with -1 / +inf.
+    1 <= k <= min(G, 128).  ``sharded=True``: as re_ranking_device (every rank holds the FULL
+    features and labels, the rows are sharded and the lists all-gathered).  There is no list form
+    of the ``local_distmat`` / ``only_local`` inputs: they are refused."""
+    from . import distributed as rd
+    from .evaluate import _as_dev_i64
+    if only_local or local_distmat is not None:
+        raise _lib.ReidmiError("re_ranking_search: the only_local / local_distmat inputs have no list form "
+                               "(re-ranked lists are computed from features only); take re_ranking_device + "
+                               "topk_rows_device")
+    labels = (q_pids, q_camids, g_pids, g_camids)
+    given = sum(a is not None for a in labels)
+    if given not in (0, 4):
+        raise _lib.ReidmiError("re_ranking_search: pass all four label arrays or none")
+    if sharded and not rd._initialized():
+        raise _lib.ReidmiError("re_ranking_search_device(sharded=True) needs an initialised torch.distributed "
+                               "process group")
+    q = _as_dev_f32(probFea)
+    Q = q.shape[0]
+    feat = torch.cat([q, _as_dev_f32(galFea)]).contiguous()
+    N = feat.shape[0]
+    check_topk(N - Q, k)
+    lab = tuple(_as_dev_i64(a) for a in labels) if given else None
+    if lab is not None and (lab[0].numel() != Q or lab[1].numel() != Q or lab[2].numel() != N - Q or
+                            lab[3].numel() != N - Q):
+        raise _lib.ReidmiError("re_ranking_search: labels must have one entry per query / gallery row")
+
+    def run():
+        return staged_rerank(HipStages(feat, Q, k1, k2, lambda_value, chunk_bytes), N, Q, int(k), lab, with_dist)
+
+    if sharded:
+        idx, dist = run()
+        return rd.gather_rows(idx, Q), (rd.gather_rows(dist, Q) if with_dist else None)
+    with rd.local():
+        return run()
+
+
+def re_ranking_search(probFea, galFea, k, k1, k2, lambda_value, q_pids=None, q_camids=None, g_pids=None,
+                      g_camids=None, with_dist=True, sharded=False, chunk_bytes=None):
+    """re_ranking_search_device, returned as numpy arrays."""
+    idx, dist = re_ranking_search_device(probFea, galFea, k, k1, k2, lambda_value, q_pids, q_camids, g_pids, g_camids,
+                                         with_dist, sharded, chunk_bytes)
+    return idx.cpu().numpy(), (dist.cpu().numpy() if with_dist else None)
 
 
 def re_ranking_sharded(probFea, galFea, k1, k2, lambda_value, chunk_bytes=None, stats=None):
