@@ -1,13 +1,68 @@
-// attention.h — the pieces the attention kernels share (attention.hip: the whole-head kernels
-// for L <= 256; attention_long.hip: the streamed-key kernels for L <= 1024): the K swizzle in
-// LDS, the single-rounding fp16 conversions, the cross-half exchanges and the widened O store.
+// attention.h — the attention host interface (for encoder.hip and resnet.hip) and the device
+// pieces the attention kernels share (attention.hip: the whole-head kernels for L <= 256;
+// attention_long.hip: the streamed-key kernels for L <= 1024): the Q prefetch, the K swizzle in
+// LDS, the accumulator key index, the fp16 conversions, the cross-half exchanges, the O store.
 #pragma once
 #include "common.h"
 
 namespace reidmi {
 
+// host interface: longest sequence of attention.hip's whole-head kernels (mhsa, mhsa_cls); longer ones, up to
+// kAttnLongMax, take attention_long.hip's streamed-key kernels (vision only, non-causal).
+constexpr int kAttnShortMax = 256, kAttnLongMax = 1024;
+// exp(x / sqrt(64)) = exp2(x * kAttnScaleLog2): 1/sqrt(64) * log2(e)
+constexpr float kAttnScaleLog2 = 0.125f * 1.4426950408889634f;
+
+// V^T row stride (elements) of an L-token sequence: LP + 4 with LP = L rounded up to 32-key
+// blocks, i.e. LP/2 + 2 dwords, which is 2 mod 4 dwords: the 32 rows of one half-wave
+// ds_read_b64 then start on 32 distinct even banks (row r at bank 2 * (r * odd mod 32)), so they
+// cover all 64 banks exactly once.  (The stride 2 mod 64 used before padded V^T by up to 60
+// elements per row: 23 % of V at L = 211.)  The QKV epilogue writes V^T with this same stride in
+// HBM, so one head's V^T is a contiguous blob for the LDS-DMA copy; 64 * (LP + 4) * 2 bytes is a
+// multiple of 512.
+constexpr int vt_stride(int L) { return (L + 31) / 32 * 32 + 4; }
+inline int attn_vt_stride(int L) { return L < 1 || L > kAttnLongMax ? -1 : vt_stride(L); }
+inline int attn_lpad(int L) { return L <= kAttnShortMax ? attn_vt_stride(L) : -1; }  // the whole-head kernels' range
+
+// q, k [nseq*H][L][64], vt [nseq*H][64][attn_vt_stride(L)] -> o [nseq*L][H*64], all fp16; the _cls
+// forms take the CLS query only, q [nseq*H][64] -> o [nseq][H*64]; attn / attn_cls pick by length
+int mhsa(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H, bool causal, hipStream_t s);
+int mhsa_long(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H, hipStream_t s);
+int attn(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H, bool causal, hipStream_t s);
+int mhsa_cls(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H, hipStream_t s);
+int mhsa_cls_long(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H, hipStream_t s);
+int attn_cls(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H, hipStream_t s);
+int64_t cls_attn_nokv_ws_bytes(int64_t nseq, int W);
+int cls_attn_nokv(const void* x, const void* rs, const void* q, const void* wqkv, const float* colsum,
+                  const float* bias, int64_t nseq, int L, int H, int W, void* ws, void* o, hipStream_t s);
+
+// ------------------------------------------------------------------------- device pieces
+typedef __attribute__((address_space(3))) void* lds_ptr_t;
+__device__ __forceinline__ uint32_t lds_addr(const void* p) {
+    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
+}
+
+// The 64 halves at qh + 0, 16, 32, 48 (a lane's four B fragments of its Q row) as inline-asm
+// loads: hipcc does not track them, so it inserts no vmcnt(0) of its own before the registers
+// are used (which would also drain the O stores and the LDS-DMA in flight).  The kernel's own
+// counted s_waitcnt retires them, and pin_q4 after that wait orders every use behind it.
+__device__ __forceinline__ void load_q4(const _Float16* qh, f16x8 (&qf)[4]) {
+    asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(qf[0]) : "v"(qh) : "memory");
+    asm volatile("global_load_dwordx4 %0, %1, off offset:32" : "=v"(qf[1]) : "v"(qh) : "memory");
+    asm volatile("global_load_dwordx4 %0, %1, off offset:64" : "=v"(qf[2]) : "v"(qh) : "memory");
+    asm volatile("global_load_dwordx4 %0, %1, off offset:96" : "=v"(qf[3]) : "v"(qh) : "memory");
+}
+__device__ __forceinline__ void pin_q4(f16x8 (&qf)[4]) {
+    asm volatile("" : "+v"(qf[0]), "+v"(qf[1]), "+v"(qf[2]), "+v"(qf[3]));
+}
+
 // K [rows][64] fp16 in LDS: the 16-byte chunk kc of row r sits at chunk kc ^ ((r >> 1) & 7)
-__device__ __forceinline__ int kswz(int r, int kc) { return r * 64 + ((kc ^ ((r >> 1) & 7)) << 3); }
+__device__ __forceinline__ int kswz_chunk(int r, int kc) { return kc ^ ((r >> 1) & 7); }
+__device__ __forceinline__ int kswz(int r, int kc) { return r * 64 + (kswz_chunk(r, kc) << 3); }
+
+// Accumulator register r of lane (ql = lane & 31, hh = lane >> 5) after S^T = K Q^T of a 32-key
+// block (v_mfma_f32_32x32x16_f16) is key acc_key(r, hh) of the block, for query ql
+__device__ __forceinline__ int acc_key(int r, int hh) { return (r & 3) + 8 * (r >> 2) + 4 * hh; }
 
 typedef float f32x2v __attribute__((ext_vector_type(2)));
 typedef _Float16 f16x2v __attribute__((ext_vector_type(2)));

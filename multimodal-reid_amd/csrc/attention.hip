@@ -16,24 +16,16 @@
 
 namespace reidmi {
 
-int attn_lpad(int L);
-
-__device__ __forceinline__ uint32_t lds_addr(const void* p) {
-    return (uint32_t)(uintptr_t)(const __attribute__((address_space(3))) void*)p;
-}
-
-typedef __attribute__((address_space(3))) void* lds_ptr_t;
-
-// One wave's block of 32 queries (row qi = block * 32 + (lane & 31)) against the head's K
+// One wave's block of 32 causal queries (row qi = block * 32 + (lane & 31)) against the head's K
 // [LP][64] and V^T [64][vstride] in LDS:
-//   S^T[key][q] = K Q^T on v_mfma_f32_32x32x16_f16; lane (q = lane&31, h = lane>>5) holds
-//     keys kb*32 + (r&3) + 8(r>>2) + 4h in s[kb][r];
+//   S^T[key][q] = K Q^T on v_mfma_f32_32x32x16_f16; lane (q = lane&31, h = lane>>5) holds key
+//     kb*32 + acc_key(r, h) in s[kb][r]; keys > qi or >= L are masked to -inf;
 //   P stays in registers: registers 8s'..8s'+7 of block kb are the B fragment of key-step s'
 //     of O^T = V^T P^T (accumulator-as-operand), V^T read with the same key permutation;
 //   O^T[d][q] comes out as 4 runs of 4 consecutive d per lane -> kAttnStores 8-byte stores (the
 //     wave's only vector-memory ops here; lanes with qi >= L store nothing).
 constexpr int kAttnStores = 8;  // (2 d blocks x 4 runs; the callers' counted waits use it)
-template <int NKB, bool CAUSAL>
+template <int NKB>
 __device__ __forceinline__ void attn_block(const _Float16* sK, const _Float16* sV, int vstride, const f16x8 (&qf)[4],
                                            int qi, int L, int64_t bh, int H, _Float16* __restrict__ o,
                                            float scale_log2) {
@@ -55,11 +47,9 @@ __device__ __forceinline__ void attn_block(const _Float16* sK, const _Float16* s
     for (int kb = 0; kb < NKB; kb++)
 #pragma unroll
         for (int r = 0; r < 16; r++) {
-            if (CAUSAL || kb == NKB - 1) {
-                const int key = kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
-                const bool ok = key < L && (!CAUSAL || key <= qi);
-                s[kb][r] = ok ? s[kb][r] : -__builtin_inff();
-            }
+            const int key = kb * 32 + acc_key(r, hh);
+            const bool ok = key < L && key <= qi;
+            s[kb][r] = ok ? s[kb][r] : -__builtin_inff();
             mx = fmaxf(mx, s[kb][r]);
         }
     mx = fmaxf(mx, __shfl_xor(mx, 32, 64));
@@ -152,7 +142,7 @@ __device__ __forceinline__ void lgkm_wait4(f16x8& a, f16x8& b, f16x8& c, f16x8& 
 }
 // mid(): called once in the P.V phase (after block NKB/2's MFMAs), after(): right after the
 // last P.V MFMA, before the O stores — the caller's prefetch for the next head goes there.
-template <int NKB, int VS_ = NKB * 32 + 4, typename Mid, typename After>
+template <int NKB, int VS_ = vt_stride(NKB * 32), typename Mid, typename After>
 __device__ __forceinline__ void attn_block_pipe(const _Float16* sK, const _Float16* sV, const f16x8 (&qf)[4], int qi,
                                                 int L, int64_t bh, int H, _Float16* __restrict__ o, float scale_log2,
                                                 Mid&& mid, After&& after) {
@@ -307,7 +297,7 @@ __device__ __forceinline__ void attn_block_pipe(const _Float16* sK, const _Float
 //   NS = 3 (the causal text shapes, NKB <= 4): a ring of three LDS stages, K/V two heads ahead
 //   and Q one head ahead — short text heads are bound by the latency of their loads (one head
 //   in flight per workgroup left the CU waiting).
-template <int NKB, bool CAUSAL, int NS = 2>
+template <int NKB, int NS = 2>
 __global__ __launch_bounds__(512) void mhsa_kernel(const _Float16* __restrict__ q, const _Float16* __restrict__ k,
                                                    const _Float16* __restrict__ vt, _Float16* __restrict__ o, int L,
                                                    int H, int vstride, int64_t nbh, float scale_log2) {
@@ -331,28 +321,16 @@ __global__ __launch_bounds__(512) void mhsa_kernel(const _Float16* __restrict__ 
         const _Float16* vh = vt + bh * 64 * (int64_t)vstride;
         for (int pc = wid; pc < kpieces; pc += nw) {
             int r = 8 * pc + (lane >> 3);
-            const int kc = (lane & 7) ^ ((r >> 1) & 7);
-            r = r < L ? r : L - 1;  // rows >= L: any finite key (masked to -inf below)
+            const int kc = kswz_chunk(r, lane & 7);
+            r = r < L ? r : L - 1;  // rows >= L: any finite key (masked to -inf)
             __builtin_amdgcn_global_load_lds(kh + (int64_t)r * 64 + kc * 8, (lds_ptr_t)(sK + pc * 512), 16, 0, 0);
         }
         for (int pc = wid; pc < vpieces; pc += nw)
             if (pc + 1 < vpieces || lane < vlast_lanes)  // never read or write past the blob
                 __builtin_amdgcn_global_load_lds(vh + pc * 512 + lane * 8, (lds_ptr_t)(sV + pc * 512), 16, 0, 0);
     };
-    // Q rows of this wave's queries; queries >= L load row L-1 (finite; never stored).
-    // Inline-asm loads: hipcc does not track them, so it inserts no vmcnt(0) of its own
-    // before the prefetched registers are used (which would also drain the O stores); the
-    // kernel's counted waits retire them, and `pin` orders every use after that wait.
-    auto load_q = [&](int64_t bh, f16x8* qf) {
-        const _Float16* qh = q + (bh * L + (qi < L ? qi : L - 1)) * 64 + hh * 8;
-        asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(qf[0]) : "v"(qh) : "memory");
-        asm volatile("global_load_dwordx4 %0, %1, off offset:32" : "=v"(qf[1]) : "v"(qh) : "memory");
-        asm volatile("global_load_dwordx4 %0, %1, off offset:64" : "=v"(qf[2]) : "v"(qh) : "memory");
-        asm volatile("global_load_dwordx4 %0, %1, off offset:96" : "=v"(qf[3]) : "v"(qh) : "memory");
-    };
-    auto pin = [&](f16x8* qf) {
-        asm volatile("" : "+v"(qf[0]), "+v"(qf[1]), "+v"(qf[2]), "+v"(qf[3]));
-    };
+    // Q rows of this wave's queries; queries >= L load row L-1 (finite; never stored)
+    auto load_q = [&](int64_t bh, f16x8 (&qf)[4]) { load_q4(q + (bh * L + (qi < L ? qi : L - 1)) * 64 + hh * 8, qf); };
     auto zero_pad = [&](int stage) {  // V^T key columns [L, LP) were DMA'd from padding
         _Float16* sV = lds + stage * stage_elems + LP * 64;
         for (int c = tid; c < 64 * (LP - L); c += blockDim.x) {
@@ -372,7 +350,7 @@ __global__ __launch_bounds__(512) void mhsa_kernel(const _Float16* __restrict__ 
         // or split), and the kernels use no scratch (tests/test_capi.py checks the ISA).
         constexpr int kRingK = LP / 8 / NKB, kRingV = 4;
         static_assert(kRingK == 4, "K: 4 one-KiB pieces per wave and head");
-        static_assert((64 * (LP + 4) * 2 + 1023) / 1024 == kRingV * NKB + 1, "V^T: 4 pieces per wave + wave 0's half");
+        static_assert((64 * vt_stride(LP) * 2 + 1023) / 1024 == kRingV * NKB + 1, "V^T: 4 pieces per wave + wave 0's half");
         constexpr int kIssue = kRingK + kRingV;        // one head's K / V^T pieces, waves 1..
         constexpr int kIssue0 = kIssue + 1;            // wave 0
         const int64_t G = gridDim.x;
@@ -388,7 +366,7 @@ __global__ __launch_bounds__(512) void mhsa_kernel(const _Float16* __restrict__ 
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kIssue0) : "memory");
         else
             asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kIssue) : "memory");
-        pin(qf);
+        pin_q4(qf);
         __builtin_amdgcn_s_barrier();
         zero_pad(0);
         asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
@@ -401,7 +379,7 @@ __global__ __launch_bounds__(512) void mhsa_kernel(const _Float16* __restrict__ 
             if (nxt2 < nbh) issue(nxt2, stage == 0 ? 2 : stage - 1);  // the stage head bh-G used
             const _Float16* sK = lds + stage * stage_elems;
             const _Float16* sV = sK + LP * 64;
-            if (wid * 32 < L) attn_block<NKB, CAUSAL>(sK, sV, vstride, qf, qi, L, bh, H, o, scale_log2);
+            if (wid * 32 < L) attn_block<NKB>(sK, sV, vstride, qf, qi, L, bh, H, o, scale_log2);
             // nxt's K / V^T (issued one head ago) and Q have landed; nxt2's K / V^T and this
             // head's O stores (the youngest ops) stay in flight
             if (wid * 32 >= L)
@@ -416,7 +394,7 @@ __global__ __launch_bounds__(512) void mhsa_kernel(const _Float16* __restrict__ 
             const int nstage = stage == 2 ? 0 : stage + 1;
             if (nxt < nbh) {
                 zero_pad(nstage);
-                pin(qn);
+                pin_q4(qn);
 #pragma unroll
                 for (int ks = 0; ks < 4; ks++) qf[ks] = qn[ks];
             }
@@ -431,7 +409,7 @@ __global__ __launch_bounds__(512) void mhsa_kernel(const _Float16* __restrict__ 
     f16x8 qf[4];
     load_q(bh, qf);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    pin(qf);
+    pin_q4(qf);
     __syncthreads();
     zero_pad(0);
     __syncthreads();
@@ -444,7 +422,7 @@ __global__ __launch_bounds__(512) void mhsa_kernel(const _Float16* __restrict__ 
         }
         const _Float16* sK = lds + stage * stage_elems;
         const _Float16* sV = sK + LP * 64;
-        if (wid * 32 < L) attn_block<NKB, CAUSAL>(sK, sV, vstride, qf, qi, L, bh, H, o, scale_log2);
+        if (wid * 32 < L) attn_block<NKB>(sK, sV, vstride, qf, qi, L, bh, H, o, scale_log2);
         // Wait for the next head's K/V DMA and Q loads only: the 8 O stores this wave just
         // issued (when it owns queries) are the youngest vector-memory ops and stay in flight
         // (vmcnt retires in issue order).
@@ -458,7 +436,7 @@ __global__ __launch_bounds__(512) void mhsa_kernel(const _Float16* __restrict__ 
         __builtin_amdgcn_s_barrier();
         if (nxt < nbh) {
             zero_pad(stage ^ 1);
-            pin(qn);
+            pin_q4(qn);
 #pragma unroll
             for (int ks = 0; ks < 4; ks++) qf[ks] = qn[ks];
         }
@@ -485,7 +463,7 @@ __global__ __launch_bounds__(NKB * 64) void mhsa_pipe_kernel(const _Float16* __r
                                                             const _Float16* __restrict__ k,
                                                             const _Float16* __restrict__ vt, _Float16* __restrict__ o,
                                                             int L, int H, int64_t nbh, float scale_log2) {
-    constexpr int LP = NKB * 32, VS = LP + 4, NW = NKB;
+    constexpr int LP = NKB * 32, VS = vt_stride(LP), NW = NKB;
     constexpr int NOLD = NW > 4 ? 4 : NW;              // waves issuing K (and V when NW <= 4)
     constexpr int STAGE = LP * 64 + 64 * VS;           // K [LP][64] then V^T [64][VS]
     constexpr int KPIECES = LP / 8;                    // 1-KiB pieces of K
@@ -498,43 +476,35 @@ __global__ __launch_bounds__(NKB * 64) void mhsa_pipe_kernel(const _Float16* __r
     const int hh = lane >> 5, ql = lane & 31;
     const int qi = wid * 32 + ql;
 
-    auto issue_k = [&](int64_t bh, int stage, int w0, int nws) {
+    auto issue_k = [&](int64_t bh, int stage, int nws) {
         _Float16* sK = lds + stage * STAGE;
         const _Float16* kh = k + bh * L * 64;
-        for (int pc = wid - w0; pc < KPIECES; pc += nws) {
+        for (int pc = wid; pc < KPIECES; pc += nws) {
             int r = 8 * pc + (lane >> 3);
-            const int kc = (lane & 7) ^ ((r >> 1) & 7);
+            const int kc = kswz_chunk(r, lane & 7);
             r = r < L ? r : L - 1;  // rows >= L: any finite key (masked to -inf)
             __builtin_amdgcn_global_load_lds(kh + (int64_t)r * 64 + kc * 8, (lds_ptr_t)(sK + pc * 512), 16, 0, 0);
         }
     };
-    auto issue_v = [&](int64_t bh, int stage, int w0, int nws) {
+    auto issue_v = [&](int64_t bh, int stage, int nws) {
         _Float16* sV = lds + stage * STAGE + LP * 64;
         const _Float16* vh = vt + bh * 64 * (int64_t)VS;
-        for (int pc = wid - w0; pc < VPIECES; pc += nws)
+        for (int pc = wid; pc < VPIECES; pc += nws)
             if (pc + 1 < VPIECES || lane < VLAST)  // never read or write past the blob
                 __builtin_amdgcn_global_load_lds(vh + pc * 512 + lane * 8, (lds_ptr_t)(sV + pc * 512), 16, 0, 0);
     };
-    // Q rows of this wave's queries (rows >= L read row L-1: finite, never stored); inline-asm
-    // loads, retired by the kernel's counted waits, every use ordered after them by pin()
-    auto load_q = [&](int64_t bh, f16x8* qf) {
-        const _Float16* qh = q + (bh * L + (qi < L ? qi : L - 1)) * 64 + hh * 8;
-        asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(qf[0]) : "v"(qh) : "memory");
-        asm volatile("global_load_dwordx4 %0, %1, off offset:32" : "=v"(qf[1]) : "v"(qh) : "memory");
-        asm volatile("global_load_dwordx4 %0, %1, off offset:64" : "=v"(qf[2]) : "v"(qh) : "memory");
-        asm volatile("global_load_dwordx4 %0, %1, off offset:96" : "=v"(qf[3]) : "v"(qh) : "memory");
-    };
-    auto pin = [&](f16x8* qf) { asm volatile("" : "+v"(qf[0]), "+v"(qf[1]), "+v"(qf[2]), "+v"(qf[3])); };
+    // Q rows of this wave's queries (rows >= L read row L-1: finite, never stored)
+    auto load_q = [&](int64_t bh, f16x8 (&qf)[4]) { load_q4(q + (bh * L + (qi < L ? qi : L - 1)) * 64 + hh * 8, qf); };
 
     int64_t bh = blockIdx.x;
     if (bh >= nbh) return;
     int stage = 0;
-    issue_k(bh, 0, 0, NW);
-    issue_v(bh, 0, 0, NW);
+    issue_k(bh, 0, NW);
+    issue_v(bh, 0, NW);
     f16x8 qf[4];
     load_q(bh, qf);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    pin(qf);
+    pin_q4(qf);
     __builtin_amdgcn_s_barrier();
     for (; bh < nbh; bh += gridDim.x) {
         const int64_t nxt = bh + gridDim.x;
@@ -542,7 +512,7 @@ __global__ __launch_bounds__(NKB * 64) void mhsa_pipe_kernel(const _Float16* __r
         f16x8 qn[4];
         if (more && wid < NOLD) {
             load_q(nxt, qn);
-            issue_k(nxt, stage ^ 1, 0, NOLD);
+            issue_k(nxt, stage ^ 1, NOLD);
         }
         const _Float16* sK = lds + stage * STAGE;
         attn_block_pipe<NKB>(
@@ -551,14 +521,14 @@ __global__ __launch_bounds__(NKB * 64) void mhsa_pipe_kernel(const _Float16* __r
                 if (more && wid >= NOLD) load_q(nxt, qn);
             },
             [&] {
-                if (more && wid < NOLD) issue_v(nxt, stage ^ 1, 0, NOLD);
+                if (more && wid < NOLD) issue_v(nxt, stage ^ 1, NOLD);
             });
         // this wave's prefetch has landed; its kAttnPipeStores O stores (the youngest
         // vector-memory ops) stay in flight.  A raw barrier (__syncthreads would drain them).
         asm volatile("s_waitcnt vmcnt(%0)" ::"n"(kAttnPipeStores) : "memory");
         __builtin_amdgcn_s_barrier();
         if (more) {
-            pin(qn);
+            pin_q4(qn);
 #pragma unroll
             for (int ks = 0; ks < 4; ks++) qf[ks] = qn[ks];
         }
@@ -626,7 +596,7 @@ __global__ __launch_bounds__(kRrWaves * 64, 1) void mhsa_rr_kernel(const _Float1
 #pragma unroll 1
         for (int pc = first; pc < KPIECES; pc += step) {
             const int r = 8 * pc + (lane >> 3);
-            const int kc = (lane & 7) ^ ((r >> 1) & 7);
+            const int kc = kswz_chunk(r, lane & 7);
             if (r < L)
                 __builtin_amdgcn_global_load_lds(kh + r * 64 + kc * 8, (lds_ptr_t)(sK + pc * 512), 16, 0, 0);
         }
@@ -637,20 +607,12 @@ __global__ __launch_bounds__(kRrWaves * 64, 1) void mhsa_rr_kernel(const _Float1
             if (pc + 1 < VPIECES || lane < VLAST)  // never read or write past the blob
                 __builtin_amdgcn_global_load_lds(vh + pc * 512 + lane * 8, (lds_ptr_t)(sV + pc * 512), 16, 0, 0);
     };
-    // Q rows of unit u's queries (rows >= L read row L-1: finite, never stored); inline-asm
-    // loads retired by the round's counted wait, every use ordered after it by pin()
+    // Q rows of unit u's queries (rows >= L read row L-1: finite, never stored)
     auto q_row = [&](int u) {
         const int j = u / NKB;
         const int qi = (u - j * NKB) * 32 + ql;
         return q + (((int64_t)b0 + (int64_t)j * G) * L + (qi < L ? qi : L - 1)) * 64 + hh * 8;
     };
-    auto load_q = [&](const _Float16* qh, f16x8* qf) {
-        asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(qf[0]) : "v"(qh) : "memory");
-        asm volatile("global_load_dwordx4 %0, %1, off offset:32" : "=v"(qf[1]) : "v"(qh) : "memory");
-        asm volatile("global_load_dwordx4 %0, %1, off offset:64" : "=v"(qf[2]) : "v"(qh) : "memory");
-        asm volatile("global_load_dwordx4 %0, %1, off offset:96" : "=v"(qf[3]) : "v"(qh) : "memory");
-    };
-    auto pin = [&](f16x8* qf) { asm volatile("" : "+v"(qf[0]), "+v"(qf[1]), "+v"(qf[2]), "+v"(qf[3])); };
 
     // prologue: the heads of round 0, and each wave's first Q
     int loaded = (NW - 1) / NKB < nh - 1 ? (NW - 1) / NKB : nh - 1;  // last head whose loads are issued
@@ -659,9 +621,9 @@ __global__ __launch_bounds__(kRrWaves * 64, 1) void mhsa_rr_kernel(const _Float1
         issue_v(head_v(j), slot(j) + KR * 64, wid, NW);
     }
     f16x8 qf[4];
-    if (wid < U) load_q(q_row(wid), qf);
+    if (wid < U) load_q4(q_row(wid), qf);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    pin(qf);
+    pin_q4(qf);
     __builtin_amdgcn_s_barrier();
     const bool older = wid < 4;
     for (int r = 0; r < R; r++) {
@@ -711,14 +673,14 @@ __global__ __launch_bounds__(kRrWaves * 64, 1) void mhsa_rr_kernel(const _Float1
         const _Float16* qn_row = q_row(un < U ? un : 0);
         f16x8 qn[4];
         if (share_a) issue_k(ka, sa, wid - w0, nws);
-        if (un < U && older) load_q(qn_row, qn);
+        if (un < U && older) load_q4(qn_row, qn);
         if (u < U) {
             const int j = u / NKB;
             const _Float16* sK = slot(j);
             attn_block_pipe<NKB, VS>(
                 sK, sK + KR * 64, qf, (u - j * NKB) * 32 + ql, L, (int64_t)b0 + (int64_t)j * G, H, o, scale_log2,
                 [&] {
-                    if (un < U && !older) load_q(qn_row, qn);
+                    if (un < U && !older) load_q4(qn_row, qn);
                     if (carry_b) issue_k(kb, sb, 0, 1);  // after this wave's S phase: its K is no longer read
                 },
                 [&] {
@@ -731,21 +693,13 @@ __global__ __launch_bounds__(kRrWaves * 64, 1) void mhsa_rr_kernel(const _Float1
         }
         __builtin_amdgcn_s_barrier();
         if (un < U) {
-            pin(qn);
+            pin_q4(qn);
 #pragma unroll
             for (int ks = 0; ks < 4; ks++) qf[ks] = qn[ks];
         }
     }
 }
 #endif  // REIDMI_TOOLS (round-robin vision attention)
-
-// V^T row stride (elements): LP + 4, i.e. LP/2 + 2 dwords, which is 2 mod 4 dwords (LP is a
-// multiple of 32): the 32 rows of one half-wave ds_read_b64 then start on 32 distinct even
-// banks (row r at bank 2 * (r * odd mod 32)), so they cover all 64 banks exactly once.  (The
-// stride 2 mod 64 used before padded V^T by up to 60 elements per row: 23 % of V at L = 211.)
-// The QKV epilogue writes V^T with this same stride in HBM, so one head's V^T is a contiguous
-// blob for the LDS-DMA copy; 64 * (LP + 4) * 2 bytes is a multiple of 512.
-static int vt_stride(int lp) { return lp + 4; }
 
 static int g_num_cu = 0;
 static int num_cu() {
@@ -760,8 +714,9 @@ static int num_cu() {
 
 template <int NKB>
 static int launch_mhsa_pipe(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H,
-                            hipStream_t s) {
-    constexpr int LP = NKB * 32, VS = LP + 4;
+                            int lpad_g, hipStream_t s) {
+    constexpr int LP = NKB * 32, VS = vt_stride(LP);
+    RM_REQUIRE(lpad_g == VS, "mhsa: v^T row stride must be reidmi_attn_lpad(L)");
     const size_t lds = 2 * ((size_t)LP * 64 * 2 + (size_t)64 * VS * 2);
     static bool attr = false;
     if (!attr) {
@@ -780,7 +735,7 @@ static int launch_mhsa_pipe(const void* q, const void* k, const void* vt, void* 
     const int64_t grid = nbh < slots ? nbh : slots;
     hipLaunchKernelGGL((mhsa_pipe_kernel<NKB>), dim3((unsigned)grid), dim3(NKB * 64), lds, s, (const _Float16*)q,
                        (const _Float16*)k, (const _Float16*)vt, (_Float16*)o, L, H, nbh,
-                       0.125f * 1.4426950408889634f);
+                       kAttnScaleLog2);
     RM_LAUNCHED();
     return OK;
 }
@@ -801,29 +756,24 @@ static int launch_mhsa_rr(const void* q, const void* k, const void* vt, void* o,
     const int64_t nbh = nseq * H;  // < 2^31 (mhsa)
     const int64_t grid = nbh < num_cu() ? nbh : num_cu();  // one workgroup per CU (LDS)
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(kRrWaves * 64), lds, s, (const _Float16*)q,
-                       (const _Float16*)k, (const _Float16*)vt, (_Float16*)o, L, H, nbh, 0.125f * 1.4426950408889634f);
+                       (const _Float16*)k, (const _Float16*)vt, (_Float16*)o, L, H, nbh, kAttnScaleLog2);
     RM_LAUNCHED();
     return OK;
 }
 #endif  // REIDMI_TOOLS
 
-template <int NKB, bool CAUSAL>
-static int launch_mhsa(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H,
-                       int lpad_g, hipStream_t s) {
-    if constexpr (!CAUSAL) {
-        RM_REQUIRE(lpad_g == vt_stride(NKB * 32), "mhsa: v^T row stride must be reidmi_attn_lpad(L)");
-        return launch_mhsa_pipe<NKB>(q, k, vt, o, nseq, L, H, s);
-    } else {  // (discarded for the pipelined shapes: mhsa_kernel<NKB, false> is not instantiated)
+template <int NKB>
+static int launch_mhsa_causal(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H,
+                              int lpad_g, hipStream_t s) {
     constexpr int LP = NKB * 32;
-    // three LDS stages for the short causal (text) shapes (mhsa_kernel NS), two otherwise
-    constexpr int NS = CAUSAL && NKB <= 4 ? 3 : 2;
+    // three LDS stages for the short (text) shapes (mhsa_kernel NS), two otherwise
+    constexpr int NS = NKB <= 4 ? 3 : 2;
     const int vs = vt_stride(LP);
     RM_REQUIRE(lpad_g == vs, "mhsa: v^T row stride must be reidmi_attn_lpad(L)");
-    RM_REQUIRE(NS == 2 || (vs == LP + 4 && (L + 31) / 32 == NKB), "mhsa: ring counts assume V^T rows of LP + 4");
+    RM_REQUIRE(NS == 2 || (vs == vt_stride(LP) && (L + 31) / 32 == NKB), "mhsa: ring counts assume V^T rows of LP + 4");
     const size_t stage = (size_t)LP * 64 * 2 + (size_t)64 * vs * 2;
     const size_t lds = NS * stage;
-    const float scale_log2 = 0.125f * 1.4426950408889634f;  // 1/sqrt(64) * log2(e)
-    auto kern = mhsa_kernel<NKB, CAUSAL, NS>;
+    auto kern = mhsa_kernel<NKB, NS>;
     static bool attr = false;
     if (!attr) {
         RM_CHECK_HIP(hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds));
@@ -831,9 +781,9 @@ static int launch_mhsa(const void* q, const void* k, const void* vt, void* o, in
     }
     const int64_t nbh = nseq * H;
     const int waves = (L + 31) / 32;
-    // Persistent grid: as many workgroups per CU as fit (LDS, VGPRs).  Vision (L = 211: 7
-    // waves, 2 x 57 KB LDS) fits one; short text rows (L <= 64: 2 waves, 2 x 17 KB) fit four,
-    // which a single workgroup per CU would leave latency-bound on its K/V loads.
+    // Persistent grid: as many workgroups per CU as fit (LDS, VGPRs).  Short text rows (L <= 64:
+    // 2 waves, 3 x 17 KB) fit several, which a single workgroup per CU would leave latency-bound
+    // on its K/V loads.
     static int occ_waves = -1, occ = 1;
     if (occ_waves != waves) {
         int n = 0;
@@ -845,10 +795,9 @@ static int launch_mhsa(const void* q, const void* k, const void* vt, void* o, in
     const int64_t grid = nbh < slots ? nbh : slots;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(64 * waves), lds, s,
                        (const _Float16*)q, (const _Float16*)k, (const _Float16*)vt, (_Float16*)o, L, H, vs, nbh,
-                       scale_log2);
+                       kAttnScaleLog2);
     RM_LAUNCHED();
     return OK;
-    }
 }
 
 // CLS query only (the last block of the inference path): one wave per (sequence, head).
@@ -921,7 +870,7 @@ int mhsa_cls(const void* q, const void* k, const void* vt, void* o, int64_t nseq
     RM_REQUIRE(lp > 0, "mhsa_cls: sequence length must be <= 256");
     const int64_t nbh = nseq * H;
     hipLaunchKernelGGL(mhsa_cls_kernel, dim3(ceil_div(nbh, 4)), dim3(256), 0, s, (const _Float16*)q, (const _Float16*)k,
-                       (const _Float16*)vt, (_Float16*)o, nbh, L, H, lp, 0.125f * 1.4426950408889634f);
+                       (const _Float16*)vt, (_Float16*)o, nbh, L, H, lp, kAttnScaleLog2);
     RM_LAUNCHED();
     return OK;
 }
@@ -1258,7 +1207,7 @@ static int launch_cls_nokv(const _Float16* x, const float2* rs, const _Float16* 
     }
     const int64_t slots = (int64_t)num_cu() * occ;
     hipLaunchKernelGGL(cls_attn_kernel<W>, dim3((unsigned)(nseq < slots ? nseq : slots)), dim3(512), ClsLds<W>::BYTES, s,
-                       x, rs, (const _Float16*)u16, (const float*)qsb, nseq, L, 0.125f * 1.4426950408889634f, z, alpha);
+                       x, rs, (const _Float16*)u16, (const float*)qsb, nseq, L, kAttnScaleLog2, z, alpha);
     RM_LAUNCHED();
     hipLaunchKernelGGL(cls_o_kernel<W>, dim3(nb), dim3(256), 0, s, (const float*)z, (const float*)alpha,
                        wqkv + (int64_t)2 * W * W, colsum + 2 * W, bias + 2 * W, nseq, o);
@@ -1279,13 +1228,6 @@ int cls_attn_nokv(const void* x, const void* rs, const void* q, const void* wqkv
              (char*)ws, (_Float16*)o, s);
 }
 
-// Smallest instantiated key-padding >= L.  Lp must also equal the vt row length the
-// QKV epilogue wrote (attn_lpad()).
-int attn_lpad(int L) {
-    if (L < 1 || L > 256) return -1;
-    return vt_stride((L + 31) / 32 * 32);  // row stride of V^T (elements), >= L
-}
-
 int mhsa(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H, bool causal,
          hipStream_t s) {
     const int lp = attn_lpad(L);
@@ -1293,8 +1235,8 @@ int mhsa(const void* q, const void* k, const void* vt, void* o, int64_t nseq, in
     RM_REQUIRE(nseq * H < (1ll << 31), "mhsa: too many (sequence, head) pairs");
 #define RM_MHSA_CASE(n)                                                                                  \
     case n:                                                                                              \
-        return causal ? launch_mhsa<n, true>(q, k, vt, o, nseq, L, H, lp, s)                            \
-                      : launch_mhsa<n, false>(q, k, vt, o, nseq, L, H, lp, s);
+        return causal ? launch_mhsa_causal<n>(q, k, vt, o, nseq, L, H, lp, s)                           \
+                      : launch_mhsa_pipe<n>(q, k, vt, o, nseq, L, H, lp, s);
     switch ((L + 31) / 32) {
         RM_MHSA_CASE(1)
         RM_MHSA_CASE(2)
@@ -1307,6 +1249,18 @@ int mhsa(const void* q, const void* k, const void* vt, void* o, int64_t nseq, in
     }
 #undef RM_MHSA_CASE
     return fail(EINVAL_, "mhsa: unsupported length");
+}
+
+// Full / CLS-row attention by length: the whole-head kernels up to kAttnShortMax tokens,
+// attention_long.hip's streamed-key kernels beyond (non-causal only).
+int attn(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H, bool causal, hipStream_t s) {
+    if (L <= kAttnShortMax) return mhsa(q, k, vt, o, nseq, L, H, causal, s);
+    RM_REQUIRE(!causal, "run_block: no causal attention beyond 256 tokens");
+    return mhsa_long(q, k, vt, o, nseq, L, H, s);
+}
+
+int attn_cls(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H, hipStream_t s) {
+    return L <= kAttnShortMax ? mhsa_cls(q, k, vt, o, nseq, L, H, s) : mhsa_cls_long(q, k, vt, o, nseq, L, H, s);
 }
 
 }  // namespace reidmi

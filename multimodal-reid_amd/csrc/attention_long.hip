@@ -12,13 +12,6 @@
 
 namespace reidmi {
 
-// V^T row stride (elements) for an L-token sequence: attention.hip's vt_stride rule (32-key
-// blocks + 4: 2 mod 4 dwords) continued past 256, so the QKV epilogue writes both alike.
-int attn_vt_stride(int L) {
-    if (L < 1 || L > 1024) return -1;
-    return (L + 31) / 32 * 32 + 4;
-}
-
 // One workgroup = kLongWaves waves = kLongWaves consecutive 32-query blocks of one head; the
 // workgroups of a head (ceil(L / 128)) are neighbours in the grid, so the head's K and V^T come
 // from L2 for all but the first.  Per key tile (kLongTile = 64 keys = two 32-key blocks):
@@ -36,7 +29,7 @@ int attn_vt_stride(int L) {
 //     l = l f + sum p, O = O f (every tile: no deferred rescale), P -> fp16, O^T += V^T P^T.
 // LDS: 2 stages x (K [64][64] + V^T [64][68]) fp16 = 33 792 B.
 constexpr int kLongWaves = 4, kLongTile = 64;
-constexpr int kLongVS = kLongTile + 4;                          // V^T tile row stride (2 mod 4 dwords)
+constexpr int kLongVS = vt_stride(kLongTile);                   // V^T tile row stride (2 mod 4 dwords)
 constexpr int kLongStage = kLongTile * 64 + 64 * kLongVS;        // halves per stage
 constexpr int kLongKPieces = kLongTile * 8 / (kLongWaves * 64);  // 16-byte K pieces per thread
 constexpr int kLongVPieces = 64 * (kLongTile / 4) / (kLongWaves * 64);  // 8-byte V^T pieces per thread
@@ -97,21 +90,15 @@ __global__ __launch_bounds__(kLongWaves * 64) void mhsa_long_kernel(const _Float
     };
 
     fetch(0);
-    // Q rows of this wave's queries (rows >= L read row L-1: finite, never stored)
-    // Inline-asm loads retired by the explicit wait below (attention.hip's load_q / pin idiom):
-    // loads hipcc tracks stay pending in its model around the loop's back edge, and it then waits
-    // for vmcnt(0) in front of every tile's S MFMAs, which also drains the tile prefetch.
+    // Q rows of this wave's queries (rows >= L read row L-1: finite, never stored), retired by
+    // the explicit wait below (load_q4, attention.h): loads hipcc tracks stay pending in its
+    // model around the loop's back edge, and it then waits for vmcnt(0) in front of every tile's
+    // S MFMAs, which also drains the tile prefetch.
     f16x8 qf[4];
-    {
-        const _Float16* qh = q + (bh * L + (qi < L ? qi : L - 1)) * 64 + hh * 8;
-        asm volatile("global_load_dwordx4 %0, %1, off" : "=v"(qf[0]) : "v"(qh) : "memory");
-        asm volatile("global_load_dwordx4 %0, %1, off offset:32" : "=v"(qf[1]) : "v"(qh) : "memory");
-        asm volatile("global_load_dwordx4 %0, %1, off offset:64" : "=v"(qf[2]) : "v"(qh) : "memory");
-        asm volatile("global_load_dwordx4 %0, %1, off offset:96" : "=v"(qf[3]) : "v"(qh) : "memory");
-    }
+    load_q4(q + (bh * L + (qi < L ? qi : L - 1)) * 64 + hh * 8, qf);
     stash(0, 0);
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
-    asm volatile("" : "+v"(qf[0]), "+v"(qf[1]), "+v"(qf[2]), "+v"(qf[3]));
+    pin_q4(qf);
     __syncthreads();
 
     float m = -__builtin_inff(), l = 0.f;
@@ -138,7 +125,7 @@ __global__ __launch_bounds__(kLongWaves * 64) void mhsa_long_kernel(const _Float
                 for (int kb = 0; kb < 2; kb++)
 #pragma unroll
                     for (int r = 0; r < 16; r++) {
-                        const int key = t * kLongTile + kb * 32 + (r & 3) + 8 * (r >> 2) + 4 * hh;
+                        const int key = t * kLongTile + kb * 32 + acc_key(r, hh);
                         s[kb][r] = key < L ? s[kb][r] : -__builtin_inff();
                     }
             }
@@ -200,7 +187,7 @@ int mhsa_long(const void* q, const void* k, const void* vt, void* o, int64_t nse
     RM_REQUIRE(nseq * H * nqc < (1ll << 31), "mhsa_long: too many (sequence, head) pairs");
     hipLaunchKernelGGL(mhsa_long_kernel, dim3((unsigned)(nseq * H * nqc)), dim3(kLongWaves * 64), 0, s,
                        (const _Float16*)q, (const _Float16*)k, (const _Float16*)vt, (_Float16*)o, L, H, stride, nqc,
-                       0.125f * 1.4426950408889634f);
+                       kAttnScaleLog2);
     RM_LAUNCHED();
     return OK;
 }
@@ -212,7 +199,7 @@ int mhsa_long(const void* q, const void* k, const void* vt, void* o, int64_t nse
 // row in key order, one fp16 rounding of the output.  V^T is read in 8-byte pieces that start
 // below L (so they end inside the row) and elements >= L are never used.
 // q [nseq*H][64], k [nseq*H][L][64], vt [nseq*H][64][stride] -> o [nseq][H*64].
-constexpr int kClsLongMax = 1024;
+constexpr int kClsLongMax = kAttnLongMax;
 
 __global__ __launch_bounds__(256) void mhsa_cls_long_kernel(const _Float16* __restrict__ q,
                                                             const _Float16* __restrict__ k,
@@ -274,8 +261,7 @@ int mhsa_cls_long(const void* q, const void* k, const void* vt, void* o, int64_t
     const int64_t nbh = nseq * H;
     RM_REQUIRE(nbh < (1ll << 31), "mhsa_cls_long: too many (sequence, head) pairs");
     hipLaunchKernelGGL(mhsa_cls_long_kernel, dim3(ceil_div(nbh, 4)), dim3(256), 0, s, (const _Float16*)q,
-                       (const _Float16*)k, (const _Float16*)vt, (_Float16*)o, nbh, L, H, stride,
-                       0.125f * 1.4426950408889634f);
+                       (const _Float16*)k, (const _Float16*)vt, (_Float16*)o, nbh, L, H, stride, kAttnScaleLog2);
     RM_LAUNCHED();
     return OK;
 }

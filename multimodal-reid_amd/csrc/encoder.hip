@@ -14,21 +14,10 @@
 // rstd * acc - mean * rstd * colsum + (b + W beta) in their epilogues (gemm.h).  Every other
 // GEMM / attention operand (patch columns, q / k / v, softmax probabilities, attention and
 // QuickGELU outputs, ln_post / ln_final rows) is fp16 too; LayerNorm statistics fp32.
+#include "attention.h"
 #include "gemm.h"
 
 namespace reidmi {
-
-int mhsa(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H, bool causal,
-         hipStream_t s);
-int attn_lpad(int L);
-// attention_long.hip: the streamed-key kernels for 256 < L <= 1024 (vision only, non-causal)
-int attn_vt_stride(int L);
-int mhsa_long(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H, hipStream_t s);
-int mhsa_cls_long(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H, hipStream_t s);
-int mhsa_cls(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H, hipStream_t s);
-int64_t cls_attn_nokv_ws_bytes(int64_t nseq, int W);
-int cls_attn_nokv(const void* x, const void* rs, const void* q, const void* wqkv, const float* colsum,
-                  const float* bias, int64_t nseq, int L, int H, int W, void* ws, void* o, hipStream_t s);
 
 // ------------------------------------------------------------------- LayerNorm
 // One wave per row; W = NV*256, each lane holds NV groups of 4 consecutive elements.
@@ -502,10 +491,6 @@ static int ln1_stats(XStats xs, char* ws, const Plan& P, int64_t M, int W, hipSt
     return row_stats((const _Float16*)(ws + P.x), M, W, W, st, s);
 }
 
-// Longest sequence of attention.hip's whole-head kernels (mhsa, mhsa_cls); longer ones, up to
-// attn_vt_stride's 1024, take attention_long.hip's streamed-key kernels.
-constexpr int kAttnShortMax = 256;
-
 // One ResidualAttentionBlock on the fp16 residual stream x [nseq*L][W].  ln_1 / ln_2 are
 // folded into the QKV / c_fc GEMMs (fp16 operands: x itself and W diag(gamma)); only the
 // per-row statistics are computed here (row_stats), never the normalised activations.
@@ -532,14 +517,9 @@ static int run_block(const reidmi_block_weights& bw, char* ws, const Plan& P, in
         ea.vt = ws + P.vt;
         ea.seq = L;
         ea.heads = H;
-        ea.lpad = attn_vt_stride(L);  // (= attn_lpad(L) up to 256 tokens)
+        ea.lpad = attn_vt_stride(L);
         if ((rc = gemm_f16(EPI_QKV, x, W, bw.qkv_w, W, M, 3 * W, W, ea, s))) return rc;
-        if (L <= kAttnShortMax) {
-            if ((rc = mhsa(ws + P.q, ws + P.k, ws + P.vt, o, nseq, L, H, causal, s))) return rc;
-        } else {
-            RM_REQUIRE(!causal, "run_block: no causal attention beyond 256 tokens");
-            if ((rc = mhsa_long(ws + P.q, ws + P.k, ws + P.vt, o, nseq, L, H, s))) return rc;
-        }
+        if ((rc = attn(ws + P.q, ws + P.k, ws + P.vt, o, nseq, L, H, causal, s))) return rc;
     }
     EpiArgs er{};
     er.out = x;
@@ -599,7 +579,7 @@ static int run_block_cls(const reidmi_block_weights& bw, char* ws, const Plan& P
     // the reassociated path covers widths 768 / 1024 (64-wide heads), L <= 224 and scratch that
     // fits the K buffer of the other path (L * W * 2 bytes per image); anything else (and
     // REIDMI_CLS_KV=1, read per call: tests switch it in-process) takes the K / V path, whose
-    // single-query kernel is mhsa_cls up to 256 tokens and mhsa_cls_long beyond
+    // single-query kernel attn_cls picks by length
     const char* kv_env = getenv("REIDMI_CLS_KV");
     const bool kv_path = (kv_env != nullptr && kv_env[0] == '1') || !(W == 768 || W == 1024) || H * 64 != W ||
                          L > 224 || cls_attn_nokv_ws_bytes(nseq, W) > nseq * L * W * 2;
@@ -624,14 +604,12 @@ static int run_block_cls(const reidmi_block_weights& bw, char* ws, const Plan& P
         kv.vt = ws + P.vt;
         kv.seq = L;
         kv.heads = H;
-        kv.lpad = attn_vt_stride(L);  // (= attn_lpad(L) up to 256 tokens)
+        kv.lpad = attn_vt_stride(L);
         kv.n_off = W;
         if ((rc = gemm_f16(EPI_QKV, x, W, (const _Float16*)bw.qkv_w + (int64_t)W * W, W, M, 2 * W, W, kv, s)))
             return rc;
         if ((rc = gemm_f16(EPI_QKV, x, ldc, bw.qkv_w, W, nseq, W, W, qa, s))) return rc;
-        if (L <= kAttnShortMax) rc = mhsa_cls(ws + P.q, ws + P.k, ws + P.vt, o, nseq, L, H, s);
-        else rc = mhsa_cls_long(ws + P.q, ws + P.k, ws + P.vt, o, nseq, L, H, s);
-        if (rc) return rc;
+        if ((rc = attn_cls(ws + P.q, ws + P.k, ws + P.vt, o, nseq, L, H, s))) return rc;
     }
     EpiArgs er{};
     er.out = x;
@@ -676,7 +654,7 @@ REIDMI_API int reidmi_layernorm(const float* x, int64_t rows, int64_t ldx, const
 REIDMI_API int64_t reidmi_vit_workspace_bytes(const reidmi_vit_weights* w, int64_t B, int full) {
     if (vit_check(w)) return -1;
     const int64_t L = 1 + (int64_t)w->grid_h * w->grid_w + w->n_ctx;
-    if (L < 1 || L > 1024) return -1;  // (attn_vt_stride's range)
+    if (L < 1 || L > kAttnLongMax) return -1;  // (attn_vt_stride's range)
     return plan(B, (int)L, w->width, attn_vt_stride((int)L), 0).total;
 }
 

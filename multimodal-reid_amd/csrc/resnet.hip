@@ -22,20 +22,15 @@
 //                      kernels of attention.hip / attention_long.hip.
 // Every kernel has a fixed per-element summation chain that does not depend on the batch size or
 // on the pixel's position in a tile, so image b of a batch equals the same image run alone.
+#include "attention.h"
 #include "common.h"
 #include "gemm.h"
 
 namespace reidmi {
 
-int mhsa(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H, bool causal,
-         hipStream_t s);
-int attn_vt_stride(int L);
-int mhsa_long(const void* q, const void* k, const void* vt, void* o, int64_t nseq, int L, int H, hipStream_t s);
-
 namespace {
 
-constexpr int kAttnShortMax = 256;  // mhsa up to here, mhsa_long beyond (encoder.hip)
-constexpr int kMaxTokens = 1024;
+constexpr int kMaxTokens = kAttnLongMax;
 
 struct ConvArgs {
     const _Float16* x;
@@ -672,9 +667,7 @@ REIDMI_API int reidmi_resnet_forward(const reidmi_resnet_weights* w, const void*
     ea.heads = w->heads;
     ea.lpad = attn_vt_stride(L);
     if ((rc = gemm_f16(EPI_QKV, tok, C, w->qkv_w, C, B * L, 3 * (int64_t)C, C, ea, s))) return rc;
-    if (L <= kAttnShortMax) rc = mhsa(ws + P.q, ws + P.k, ws + P.vt, o, B, L, w->heads, false, s);
-    else rc = mhsa_long(ws + P.q, ws + P.k, ws + P.vt, o, B, L, w->heads, s);
-    if (rc) return rc;
+    if ((rc = attn(ws + P.q, ws + P.k, ws + P.vt, o, B, L, w->heads, false, s))) return rc;
     EpiArgs ec{};
     ec.bias = w->c_b;
     ec.ldc = E;

@@ -134,6 +134,17 @@ def test_attn_lpad_every_length():
         assert T.reidmi_attn_lpad(L) < 0, L
 
 
+def test_attn_stride_rule_has_one_definition():
+    """reidmi_attn_vt_stride is the rule for 1..1024, reidmi_attn_lpad the same rule cut at 256."""
+    T = _tools()
+    for L in range(1, 1025):
+        assert T.reidmi_attn_vt_stride(L) == (L + 31) // 32 * 32 + 4, L
+    for L in range(1, 257):
+        assert T.reidmi_attn_lpad(L) == T.reidmi_attn_vt_stride(L), L
+    assert T.reidmi_attn_lpad(0) == -1 and T.reidmi_attn_lpad(257) == -1
+    assert T.reidmi_attn_vt_stride(0) == -1 and T.reidmi_attn_vt_stride(1025) == -1
+
+
 @pytest.mark.parametrize("L", [0, 257])
 @pytest.mark.parametrize("causal", [0, 1])
 def test_mhsa_refuses_unsupported_lengths(L, causal):
