@@ -2,9 +2,15 @@
 
 This is the product's only route to compute: there is no CPU or PyTorch fallback.
 If the library is missing or no GPU is present, calls raise loudly.
+
+The headers are the one written copy of the ABI: every entry point's argtypes / restype and
+every struct's ctypes.Structure are read from include/reidmi.h (and reidmi_tools.h).
+build_lib.manifest_matches() ties a loaded library to those same header files.
 """
 import ctypes
+import functools
 import os
+import re
 
 import torch
 
@@ -12,127 +18,10 @@ PKG = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(PKG, "libreidmi.so")
 TOOLS_LIB_PATH = os.path.join(PKG, "libreidmi_tools.so")  # tests / A-B tools only (reidmi_tools.h)
 
-_vp = ctypes.c_void_p
-_i64 = ctypes.c_int64
-_i32 = ctypes.c_int
-_f32 = ctypes.c_float
-_u16 = ctypes.c_uint16
-
-# name -> argtypes (all return int status)
-# entry points returning int64 besides the *_bytes sizes
-INT64_RESULT = {"reidmi_rr_rank_rows_f16_pass_rows"}
-
-SIGNATURES = {
-    "reidmi_row_sqnorm_f32": [_vp, _i64, _i64, _i64, _vp, _vp],
-    "reidmi_l2norm_f32": [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp],
-    "reidmi_distmat_f32": [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp],
-    "reidmi_cosine_f32": [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _vp],
-    "reidmi_distmat_f16_workspace_bytes": [_i64, _i64, _i64],
-    "reidmi_distmat_f16": [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp],
-    "reidmi_topk_rows_f32": [_vp, _i64, _i64, _i64, _vp, _i32, _vp, _vp, _i64, _vp],
-    "reidmi_search_workspace_bytes": [_i64, _i64, _i64, _i32],
-    "reidmi_search_f32": [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64,
-                          _vp],
-    "reidmi_eval_rows": [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp],
-    "reidmi_eval_rows_workspace_bytes": [_i64],
-    "reidmi_gemm_f16": [_i32, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _vp],
-    "reidmi_rerank_workspace_bytes": [_i64, _i64, _i32, _i32, _i32, _i32],
-    "reidmi_rerank": [_vp, _i64, _i64, _i64, _i64, _i32, _i32, _u16, _f32, _vp, _i64, _vp, _i64, _vp, _vp],
-    "reidmi_rerank_from_dist": [_vp, _vp, _i64, _i64, _i32, _i32, _i32, _u16, _f32, _vp, _i64, _vp, _i64, _vp,
-                                _vp],
-    "reidmi_rr_caps": [_i64, _i32, _i32, _vp, _vp, _vp, _vp],
-    "reidmi_rr_rank_rows": [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _i64, _vp],
-    "reidmi_rr_feat16": [_vp, _i64, _i64, _i64, _vp, _i64, _i64, _vp, _vp],
-    "reidmi_rr_norm_max": [_vp, _vp, _i64, _vp, _vp],
-    "reidmi_rr_rank_rows_f16": [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp, _vp,
-                                _vp, _i64, _vp],
-    "reidmi_rr_rank_rows_f16_ex": [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _i32, _vp, _vp,
-                                   _vp, _vp, _i64, _i32, _vp],
-    "reidmi_rr_rank_rows_f16_pass_rows": [_i64, _i64, _i64, _i32, _i32],
-    "reidmi_rr_tri_plan": [_i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp],
-    "reidmi_rr_tri_init": [_vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp],
-    "reidmi_rr_tri_sample": [_vp, _i64, _i64, _vp, _vp, _vp, _i64, _i64, _i32, _vp, _vp, _i64, _i64, _i64, _vp, _i64,
-                             _vp, _vp, _vp, _i32, _vp],
-    "reidmi_rr_tri_survivors": [_vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i64, _i64, _vp, _vp, _i32, _vp],
-    "reidmi_rr_sv_select": [_vp, _vp, _i32, _vp, _vp, _i64, _i64, _vp, _i64, _i64, _i32, _vp, _vp, _vp, _vp],
-    "reidmi_rr_sv_pack": [_vp, _vp, _i32, _i64, _vp, _vp, _vp],
-    "reidmi_rr_sv_merge": [_vp, _vp, _i32, _i64, _vp, _vp, _vp, _vp],
-    "reidmi_rr_v_rows": [_vp, _i64, _i64, _i64, _vp, _vp, _vp, _i32, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _i64, _vp,
-                         _vp],
-    "reidmi_rr_row_offsets": [_vp, _i64, _vp, _vp],
-    "reidmi_rr_pack": [_vp, _vp, _vp, _i64, _i64, _vp, _vp, _vp, _vp],
-    "reidmi_rr_qe_rows": [_vp, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp, _vp],
-    "reidmi_rr_qe_deferred": [_vp, _i32, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _vp, _vp, _vp, _vp,
-                              _vp, _i64, _vp, _vp],
-    "reidmi_rr_csc_workspace_bytes": [_i64, _i64],
-    "reidmi_rr_csc": [_i64, _vp, _vp, _vp, _i64, _vp, _vp, _vp, _vp, _i64, _vp],
-    "reidmi_rr_jaccard_rows": [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
-                               _u16, _f32, _vp, _i64, _vp, _i64, _vp, _i64, _vp],
-    "reidmi_rr_jaccard_bounds_bytes": [_i64, _i64],
-    "reidmi_rr_jaccard_topk_workspace_bytes": [_i64, _i64, _i32],
-    "reidmi_rr_jaccard_topk_rows": [_vp, _i64, _i64, _i64, _vp, _vp, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp,
-                                    _u16, _f32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp, _i64, _vp, _i64, _vp,
-                                    _i64, _vp],
-    "reidmi_rowmax_f32": [_vp, _i64, _i64, _i64, _vp, _vp],
-    "reidmi_nonzero_i32": [_vp, _i64, _vp, _vp, _vp],
-    "reidmi_gather_rows_f32": [_vp, _i64, _i64, _i64, _vp, _i64, _vp, _i64, _vp],
-    "reidmi_attn_lpad": [_i32],
-    "reidmi_attn_vt_stride": [_i32],
-    "reidmi_mhsa_long_f16": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp],
-    "reidmi_prof_enable": [_i32],
-    "reidmi_prof_collect": [_i32, _vp, _vp, _vp],
-    "reidmi_prof_collect_min": [_i32, ctypes.c_double, _vp, _vp, _vp],
-    "reidmi_mhsa_f16": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp],
-    "reidmi_layernorm": [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _f32, _vp, _i64, _vp, _i64, _vp],
-    "reidmi_row_stats_f16": [_vp, _i64, _i64, _i64, _vp, _vp, _vp],
-    "reidmi_gemm_f16_resid_partials": [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _vp, _vp],
-    "reidmi_conv2d_f16": [_vp, _i64, _i32, _i32, _i32, _vp, _i32, _i32, _i32, _vp, _vp, _vp, _i32, _vp, _vp],
-    "reidmi_avgpool2_f16": [_vp, _i64, _i32, _i32, _i32, _vp, _vp],
-    "reidmi_feature_tta_avg": [_vp, _vp, _vp, _vp, _i64, _i64, _i64, _vp, _i64, _vp],
-    "reidmi_feature_tta_mm": [_vp, _vp, _vp, _vp, _vp, _i64, _i64, _i64, _i64, _vp, _i64, _vp],
-    "reidmi_class_mean_normalize": [_vp, _vp, _i64, _i64, _vp, _vp],
-    "reidmi_prompt_build": [_vp, _i32, _vp, _i32, _vp, _i64, _vp, _i32, _i64, _i32, _vp, _vp, _vp],
-    "reidmi_preprocess_u8": [_vp, _vp, _i64, _i32, _i32, _i32, _i32, _vp, _vp, _i32, _vp, _vp],
-    "reidmi_preprocess_lds_size": [_i32, _i32, _i32, _i32, _vp],
-    "reidmi_jpeg_plan": [_vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
-    "reidmi_jpeg_decode": [_vp, _vp, _vp, _i64, _vp, _i64, _vp, _vp, _vp],
-    "reidmi_files_size": [_vp, _i64, _vp, _i32],
-    "reidmi_files_read": [_vp, _i64, _vp, _vp, _vp, _i32],
-    "reidmi_bytes_gather": [_vp, _i64, _vp, _vp, _i32],
-    "reidmi_comm_unique_id": [_vp],
-    "reidmi_comm_init": [_vp, _i32, _i32, _vp, _i32],
-    "reidmi_comm_destroy": [_vp],
-    "reidmi_comm_rank": [_vp, _vp, _vp],
-    "reidmi_comm_allgather_rows_scratch_bytes": [_i32, _i64, _i64],
-    "reidmi_comm_allgather_rows": [_vp, _vp, _i64, _i64, _vp, _vp, _i64, _vp],
-    "reidmi_comm_allreduce": [_vp, _vp, _vp, _i64, _i32, _vp],
-}
-# libreidmi_tools.so only (include/reidmi_tools.h): forced kernel variants for tests / A-B timing
-TOOLS_SIGNATURES = {
-    "reidmi_distmat_f32_variant": [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _vp, _i64, _vp, _i32, _vp],
-    "reidmi_search_ex_workspace_bytes": [_i64, _i64, _i64, _i32, _i32, _i32],
-    "reidmi_search_f32_ex": [_vp, _i64, _i64, _vp, _i64, _i64, _i64, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i64, _vp,
-                             _i64, _i32, _i32, _vp, _vp],
-    "reidmi_gemm_f16_tiled": [_i32, _vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp],
-    "reidmi_gemm_f16_w4": [_vp, _i64, _vp, _i64, _i64, _i64, _i64, _vp, _vp, _i64, _i32, _vp],
-    "reidmi_gemm_f16_qkv": [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _vp, _vp, _vp, _vp, _vp, _vp, _i32, _vp],
-    "reidmi_mhsa_f16_rr": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp],
-    "reidmi_mhsa_cls_f16": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp],
-    "reidmi_mhsa_cls_long_f16": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _vp],
-    "reidmi_cls_attn_nokv_ws_bytes": [_i64, _i32],
-    "reidmi_cls_attn_nokv_f16": [_vp, _vp, _vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _vp, _i64, _vp, _vp],
-    "reidmi_gemm_f16_qkv_ex": [_vp, _i64, _vp, _i64, _i64, _i32, _i32, _i64, _i64, _vp, _vp, _vp, _vp, _vp, _vp, _i32,
-                               _i32, _i32, _vp],
-    "reidmi_im2col_f16": [_vp, _i32, _i64, _i32, _i32, _i32, _i32, _i32, _i32, _i32, _vp, _vp, _vp],
-    "reidmi_patch_embed_f16": [_vp, _vp, _vp, _vp, _vp, _i32, _i64, _i32, _i32, _i32, _vp, _i32, _vp],
-    "reidmi_layernorm_f16": [_vp, _i64, _i64, _vp, _i64, _vp, _vp, _f32, _vp, _i64, _vp, _i64, _vp, _i64, _vp, _vp],
-    "reidmi_text_embed_f16": [_vp, _vp, _vp, _vp, _i64, _i32, _i32, _i32, _i64, _vp, _vp, _vp],
-}
-# entry points with struct arguments are typed in model.py (reidmi_vit_*, reidmi_text_*, reidmi_resnet_*)
-STRUCT_ENTRY_POINTS = ("reidmi_vit_workspace_bytes", "reidmi_vit_forward", "reidmi_text_workspace_bytes",
-                       "reidmi_text_forward", "reidmi_vit_pack_bytes", "reidmi_vit_weights_pack",
-                       "reidmi_text_pack_bytes", "reidmi_text_weights_pack", "reidmi_resnet_pack_bytes",
-                       "reidmi_resnet_weights_pack", "reidmi_resnet_workspace_bytes", "reidmi_resnet_forward")
+_SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
+            "double": ctypes.c_double, "uint16_t": ctypes.c_uint16}
+_POINTEES = ("void", "char", "uint8_t")  # known only behind a pointer
+_RESULTS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "char*": ctypes.c_char_p}
 
 _LIB = None
 _TOOLS = None
@@ -140,6 +29,102 @@ _TOOLS = None
 
 class ReidmiError(RuntimeError):
     pass
+
+
+def _ctype(ctype, types, where):
+    """Scalars by value; a pointer to a header struct is POINTER(its class); every other pointer
+    (to a scalar, void, char, a handle) is c_void_p, so callers pass data_ptr() ints and byref()."""
+    base = re.sub(r"\bconst\b|\*|\s+", "", ctype)
+    stars = ctype.count("*")
+    known = types.get(base)
+    if stars == 0 and known is not None:
+        return known
+    if stars == 1 and isinstance(known, type) and issubclass(known, ctypes.Structure):
+        return ctypes.POINTER(known)
+    if stars >= 1 and (known is not None or base in _POINTEES):
+        return ctypes.c_void_p
+    raise ReidmiError(f"reidmi header: unknown type `{ctype.strip()}` in `{where}`")
+
+
+def parse_header(text, types=None):
+    """(types, prototypes) of a header in the style of include/reidmi.h, read as C.
+    types: {C name: ctypes type} of the scalars, each `typedef struct NAME {...} NAME;` (a
+    ctypes.Structure with the header's field names) and each opaque handle typedef, on top of the
+    `types` of an included header.  prototypes: {name: (restype, argtypes)}.  Whatever it does not
+    know raises ReidmiError naming the declaration: nothing is guessed and nothing skipped."""
+    types = dict(_SCALARS if types is None else types)
+    text = re.sub(r"/\*.*?\*/|//[^\n]*", " ", text, flags=re.S)
+    text = re.sub(r"^[ \t]*#ifdef __cplusplus\n.*?^[ \t]*#endif[^\n]*$", " ", text, flags=re.S | re.M)
+    text = re.sub(r"^[ \t]*#[^\n]*$", " ", text, flags=re.M)
+
+    def struct(m):
+        name, body = m.group(1), m.group(2)
+        if m.group(3) != name:
+            raise ReidmiError(f"reidmi header: typedef struct {name} is named {m.group(3)}")
+        fields = []
+        for decl in filter(None, (" ".join(d.split()) for d in body.split(";"))):
+            f = re.fullmatch(r"(.+?[\s*])\s*(\w+(?:\[\d+\])?(?:\s*,\s*\w+(?:\[\d+\])?)*)", decl)
+            if not f or ("*" in f.group(1) and "," in f.group(2)):
+                raise ReidmiError(f"reidmi header: cannot parse field `{decl}` of {name}")
+            ctype = _ctype(f.group(1), types, f"{name}: {decl}")
+            for d in re.split(r"\s*,\s*", f.group(2)):
+                field, _, dim = d.rstrip("]").partition("[")
+                fields.append((field, ctype * int(dim) if dim else ctype))
+        types[name] = type(name, (ctypes.Structure,), {"_fields_": fields})
+        return " "
+
+    text = re.sub(r"typedef\s+struct\s+(\w+)\s*\{([^{}]*)\}\s*(\w+)\s*;", struct, text)
+    protos = {}
+    for decl in filter(None, (" ".join(d.split()) for d in text.split(";"))):
+        handle = re.fullmatch(r"typedef struct \w+ ?\* ?(\w+)", decl)
+        if handle:
+            types[handle.group(1)] = ctypes.c_void_p
+            continue
+        p = re.fullmatch(r"(.+?[\s*])\s*(reidmi_\w+) ?\(([^()]*)\)", decl)
+        if not p:
+            raise ReidmiError(f"reidmi header: cannot parse declaration `{decl}`")
+        restype = _RESULTS.get(re.sub(r"\bconst\b|\s+", "", p.group(1)))
+        if restype is None:
+            raise ReidmiError(f"reidmi header: unknown result type `{p.group(1).strip()}` in `{decl}`")
+        argtypes = []
+        for arg in ([] if p.group(3).strip() == "void" else p.group(3).split(",")):
+            a = re.fullmatch(r"(.+?[\s*])\s*\w+", arg.strip())
+            if not a:
+                raise ReidmiError(f"reidmi header: cannot parse argument `{arg.strip()}` in `{decl}`")
+            argtypes.append(_ctype(a.group(1), types, decl))
+        protos[p.group(2)] = (restype, argtypes)
+    return types, protos
+
+
+@functools.lru_cache(maxsize=None)
+def _abi():
+    from . import build_lib
+
+    def read(name):
+        with open(os.path.join(build_lib.INCLUDE, name)) as f:
+            return f.read()
+    types, product = parse_header(read("reidmi.h"))
+    _, tools = parse_header(read("reidmi_tools.h"), types)
+    return types, product, tools
+
+
+def declarations(tools=False):
+    """{entry point: (restype, argtypes)} of include/reidmi.h, with reidmi_tools.h's for tools."""
+    _, product, extra = _abi()
+    return dict(product, **extra) if tools else dict(product)
+
+
+def structs():
+    """{C struct name: its ctypes.Structure} of include/reidmi.h."""
+    return {n: t for n, t in _abi()[0].items() if isinstance(t, type) and issubclass(t, ctypes.Structure)}
+
+
+def bind(cdll, tools=False):
+    """Type every entry point the header(s) declare on an opened library (a missing one raises)."""
+    for name, (restype, argtypes) in declarations(tools).items():
+        fn = getattr(cdll, name)
+        fn.restype, fn.argtypes = restype, argtypes
+    return cdll
 
 
 def _open(path, tools):
@@ -150,15 +135,7 @@ def _open(path, tools):
     if not build_lib.manifest_matches(tools):
         raise ReidmiError(f"{path} was not built from the sources next to it (its manifest differs): "
                           "run `python __graft_entry__.py build`")
-    L = ctypes.CDLL(path)
-    L.reidmi_last_error.restype = ctypes.c_char_p
-    L.reidmi_abi_version.restype = _i32
-    table = dict(SIGNATURES, **TOOLS_SIGNATURES) if tools else SIGNATURES
-    for name, args in table.items():
-        fn = getattr(L, name)
-        fn.argtypes = args
-        fn.restype = _i64 if name.endswith("_bytes") or name in INT64_RESULT else _i32
-    return L
+    return bind(ctypes.CDLL(path), tools)
 
 
 def load():
@@ -179,18 +156,15 @@ def load_tools():
     return _TOOLS
 
 
-def call(name, *args):
-    L = load()
+def call(name, *args, tools=False):
+    L = load_tools() if tools else load()
     rc = getattr(L, name)(*args)
     if rc != 0:
         raise ReidmiError(f"{name} failed ({rc}): {L.reidmi_last_error().decode()}")
 
 
 def call_tools(name, *args):
-    L = load_tools()
-    rc = getattr(L, name)(*args)
-    if rc != 0:
-        raise ReidmiError(f"{name} failed ({rc}): {L.reidmi_last_error().decode()}")
+    call(name, *args, tools=True)
 
 
 def ptr(t):

@@ -28,107 +28,24 @@ import torch
 
 from . import _lib
 
-_vp = ctypes.c_void_p
-_i32 = ctypes.c_int32
-
-
-class BlockWeights(ctypes.Structure):
-    _fields_ = [(n, _vp) for n in ("ln1_w", "ln1_b", "qkv_w", "qkv_b", "out_w", "out_b", "ln2_w", "ln2_b",
-                                   "fc1_w", "fc1_b", "fc2_w", "fc2_b", "prompt", "qkv_s", "fc1_s")]
-
-
-class VitWeights(ctypes.Structure):
-    _fields_ = [(n, _i32) for n in ("width", "layers", "heads", "patch", "stride", "out_dim", "grid_h", "grid_w",
-                                    "n_ctx", "kpad")] + \
-               [(n, _vp) for n in ("conv_w", "class_emb", "pos_emb", "ln_pre_w", "ln_pre_b", "ln_post_w",
-                                   "ln_post_b", "proj_t", "vpt")] + [("blocks", ctypes.POINTER(BlockWeights))]
-
-
-class TextWeights(ctypes.Structure):
-    _fields_ = [(n, _i32) for n in ("width", "layers", "heads", "ctx", "vocab", "out_dim", "n_ctx")] + \
-               [(n, _vp) for n in ("tok_emb", "pos_emb", "ln_final_w", "ln_final_b", "proj_t")] + \
-               [("blocks", ctypes.POINTER(BlockWeights))]
-
-
-class BlockSrc(ctypes.Structure):  # reidmi_block_src
-    _fields_ = [(n, _vp) for n in ("ln_1_w", "ln_1_b", "in_proj_w", "in_proj_b", "out_proj_w", "out_proj_b", "ln_2_w",
-                                   "ln_2_b", "c_fc_w", "c_fc_b", "c_proj_w", "c_proj_b", "vpt_shallow")]
-
-
-class VitSrc(ctypes.Structure):  # reidmi_vit_src
-    _fields_ = [(n, _i32) for n in ("width", "layers", "patch", "stride", "out_dim", "grid_h", "grid_w", "n_ctx")] + \
-               [(n, _vp) for n in ("conv1_w", "class_embedding", "positional_embedding", "ln_pre_w", "ln_pre_b",
-                                   "ln_post_w", "ln_post_b", "proj", "vpt")] + [("blocks", ctypes.POINTER(BlockSrc))]
-
-
-class TextSrc(ctypes.Structure):  # reidmi_text_src
-    _fields_ = [(n, _i32) for n in ("width", "layers", "ctx", "vocab", "out_dim", "n_ctx")] + \
-               [(n, _vp) for n in ("token_embedding", "positional_embedding", "ln_final_w", "ln_final_b",
-                                   "text_projection")] + [("blocks", ctypes.POINTER(BlockSrc))]
-
-
-class ConvWeights(ctypes.Structure):  # reidmi_conv_weights
-    _fields_ = [(n, _vp) for n in ("w", "scale", "shift")] + [(n, _i32) for n in ("cin", "cout", "k", "stride")]
-
-
-class BottleneckWeights(ctypes.Structure):  # reidmi_bottleneck_weights
-    _fields_ = [(n, ConvWeights) for n in ("conv1", "conv2", "conv3", "down")] + \
-               [(n, _i32) for n in ("stride", "has_down")]
-
-
-class ResnetWeights(ctypes.Structure):  # reidmi_resnet_weights
-    _fields_ = [(n, _i32) for n in ("width", "embed", "heads", "out_dim", "grid_h", "grid_w")] + \
-               [("layers", _i32 * 4), ("stem", ConvWeights * 3)] + \
-               [(n, _vp) for n in ("pos_emb", "qkv_w", "qkv_b", "c_w", "c_b")] + \
-               [("blocks", ctypes.POINTER(BottleneckWeights)), ("tta_pad", ctypes.c_float * 3)]
-
-
-class ConvBnSrc(ctypes.Structure):  # reidmi_convbn_src
-    _fields_ = [(n, _vp) for n in ("conv_w", "bn_w", "bn_b", "bn_mean", "bn_var")]
-
-
-class BottleneckSrc(ctypes.Structure):  # reidmi_bottleneck_src
-    _fields_ = [(n, ConvBnSrc) for n in ("conv1", "conv2", "conv3", "down")]
-
-
-class ResnetSrc(ctypes.Structure):  # reidmi_resnet_src
-    _fields_ = [(n, _i32) for n in ("width", "out_dim", "grid_h", "grid_w")] + \
-               [("layers", _i32 * 4), ("stem", ConvBnSrc * 3)] + \
-               [(n, _vp) for n in ("positional_embedding", "q_w", "q_b", "k_w", "k_b", "v_w", "v_b", "c_w", "c_b")] + \
-               [("blocks", ctypes.POINTER(BottleneckSrc))]
-
-
-_SIG = {
-    "reidmi_resnet_pack_bytes": ([ctypes.POINTER(ResnetSrc)], ctypes.c_int64),
-    "reidmi_resnet_weights_pack": ([ctypes.POINTER(ResnetSrc), _vp, ctypes.c_int64, ctypes.POINTER(ResnetWeights),
-                                    ctypes.POINTER(BottleneckWeights), _vp], ctypes.c_int),
-    "reidmi_resnet_workspace_bytes": ([ctypes.POINTER(ResnetWeights), ctypes.c_int64, ctypes.c_int, ctypes.c_int,
-                                       ctypes.c_int], ctypes.c_int64),
-    "reidmi_resnet_forward": ([ctypes.POINTER(ResnetWeights), _vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
-                               ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp],
-                              ctypes.c_int),
-    "reidmi_vit_pack_bytes": ([ctypes.POINTER(VitSrc)], ctypes.c_int64),
-    "reidmi_vit_weights_pack": ([ctypes.POINTER(VitSrc), _vp, ctypes.c_int64, ctypes.POINTER(VitWeights),
-                                 ctypes.POINTER(BlockWeights), _vp], ctypes.c_int),
-    "reidmi_text_pack_bytes": ([ctypes.POINTER(TextSrc)], ctypes.c_int64),
-    "reidmi_text_weights_pack": ([ctypes.POINTER(TextSrc), _vp, ctypes.c_int64, ctypes.POINTER(TextWeights),
-                                  ctypes.POINTER(BlockWeights), _vp], ctypes.c_int),
-    "reidmi_vit_workspace_bytes": ([ctypes.POINTER(VitWeights), ctypes.c_int64, ctypes.c_int], ctypes.c_int64),
-    "reidmi_vit_forward": ([ctypes.POINTER(VitWeights), _vp, ctypes.c_int, ctypes.c_int64, ctypes.c_int,
-                            ctypes.c_int, _vp, ctypes.c_int, _vp, _vp, _vp, _vp, ctypes.c_int64, _vp], ctypes.c_int),
-    "reidmi_text_workspace_bytes": ([ctypes.POINTER(TextWeights), ctypes.c_int64], ctypes.c_int64),
-    "reidmi_text_forward": ([ctypes.POINTER(TextWeights), _vp, _vp, ctypes.c_int64, ctypes.c_int, _vp, _vp,
-                             ctypes.c_int64, _vp], ctypes.c_int),
-}
+# the structs of include/reidmi.h, as _lib derives them from the header (field names are the header's)
+_S = _lib.structs()
+BlockWeights = _S["reidmi_block_weights"]
+VitWeights = _S["reidmi_vit_weights"]
+TextWeights = _S["reidmi_text_weights"]
+BlockSrc = _S["reidmi_block_src"]
+VitSrc = _S["reidmi_vit_src"]
+TextSrc = _S["reidmi_text_src"]
+ConvWeights = _S["reidmi_conv_weights"]
+BottleneckWeights = _S["reidmi_bottleneck_weights"]
+ResnetWeights = _S["reidmi_resnet_weights"]
+ConvBnSrc = _S["reidmi_convbn_src"]
+BottleneckSrc = _S["reidmi_bottleneck_src"]
+ResnetSrc = _S["reidmi_resnet_src"]
 
 
 def _fn(name):
-    L = _lib.load()
-    f = getattr(L, name)
-    if name in _SIG and getattr(f, "_reidmi_typed", None) is None:
-        f.argtypes, f.restype = _SIG[name]
-        f._reidmi_typed = True
-    return f
+    return getattr(_lib.load(), name)
 
 
 def _t(a):

@@ -1,5 +1,5 @@
 """CPU-side checks of the drop-in boundary: libreidmi.so loads and exports every entry
-point include/reidmi.h declares, and the ctypes table in _lib.py covers them all; the tools
+point include/reidmi.h declares, each bound by _lib.py with the types the header states; the tools
 library (include/reidmi_tools.h) adds exactly its forced-variant entry points, which the
 product library does not export.  No compute calls (no GPU here)."""
 import ctypes
@@ -39,11 +39,20 @@ def test_library_exports_every_declared_symbol():
     assert L.reidmi_abi_version() >= 1
 
 
-def test_ctypes_table_matches_header():
+def _assert_bound(L, decls):
+    for name, (restype, argtypes) in decls.items():
+        fn = getattr(L, name)
+        assert fn.restype is restype, name
+        assert list(fn.argtypes) == list(argtypes), name
+
+
+def test_every_prototype_is_bound_with_the_parsed_types():
+    """Every prototype of reidmi.h is typed on the loaded product library exactly as the header
+    parses; the name set is cross-checked by this file's own regex."""
     from multimodal_reid_amd import _lib
-    names = set(declared()) - {"reidmi_last_error", "reidmi_abi_version"}
-    covered = set(_lib.SIGNATURES) | set(_lib.STRUCT_ENTRY_POINTS)
-    assert names == covered, names ^ covered
+    decls = _lib.declarations()
+    assert set(decls) == set(declared()), set(decls) ^ set(declared())
+    _assert_bound(_lib.load(), decls)
 
 
 def test_tools_library_exports_variants_product_does_not():
@@ -52,7 +61,9 @@ def test_tools_library_exports_variants_product_does_not():
     import torch  # noqa: F401
     from multimodal_reid_amd import _lib
     tools = declared(TOOLS_HEADER)
-    assert set(tools) == set(_lib.TOOLS_SIGNATURES)
+    decls = _lib.declarations(tools=True)
+    assert set(tools) == set(decls) - set(_lib.declarations())
+    _assert_bound(_lib.load_tools(), decls)
     assert not set(tools) & set(declared())
     P, T = ctypes.CDLL(LIB), ctypes.CDLL(TOOLS_LIB)
     assert not [n for n in tools if hasattr(P, n)], "the product library must not export the A/B variants"

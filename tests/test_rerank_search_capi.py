@@ -35,8 +35,9 @@ def test_symbols_in_header_library_and_table():
     L = _lib.load()
     for name in NAMES:
         assert re.search(r"\b%s\s*\(" % name, txt), name
-        assert name in _lib.SIGNATURES and hasattr(L, name), name
-    assert len(_lib.SIGNATURES[NAMES[0]]) == 32  # reidmi_rr_jaccard_rows' 24, minus out, plus k, labels, lists, ws
+        assert name in _lib.declarations() and hasattr(L, name), name
+    # reidmi_rr_jaccard_rows' 24, minus out, plus k, labels, lists, ws
+    assert len(getattr(L, NAMES[0]).argtypes) == 32
     assert L.reidmi_abi_version() >= 5
 
 

@@ -23,13 +23,7 @@ SHAPES = {"cfc": (3072, 768, 1, True), "qkv": (2304, 768, 0, True), "out": (768,
 
 
 def open_lib(path):
-    lib = ctypes.CDLL(os.path.abspath(path))
-    lib.reidmi_last_error.restype = ctypes.c_char_p
-    for name, args in L.SIGNATURES.items():
-        fn = getattr(lib, name)
-        fn.argtypes = args
-        fn.restype = ctypes.c_int64 if name.endswith("_bytes") or name in L.INT64_RESULT else ctypes.c_int32
-    return lib
+    return L.bind(ctypes.CDLL(os.path.abspath(path)))
 
 
 def main():

@@ -2,7 +2,6 @@
 (tools/build_variant.py NAME gemm.hip -DREIDMI_TOOLS -DW4_VAR_...): the mainloop (no stores) of
 each build on the encoder's shapes, interleaved rounds.
     python tools/w4_var_ab.py LIB.so[,LIB2.so,...] [ROUNDS] [M]"""
-import ctypes
 import os
 import sys
 
@@ -22,9 +21,9 @@ SHAPES = [("cfc", 3072, 768), ("projp", 768, 3072)]
 def main():
     libs = []
     for p in sys.argv[1].split(","):
-        lib = open_lib(p)
-        lib.reidmi_gemm_f16_w4.argtypes = L.TOOLS_SIGNATURES["reidmi_gemm_f16_w4"]
-        lib.reidmi_gemm_f16_w4.restype = ctypes.c_int32
+        lib = open_lib(p)  # a variant build: the product entry points plus gemm.hip's tools section
+        w4 = lib.reidmi_gemm_f16_w4
+        w4.restype, w4.argtypes = L.declarations(tools=True)["reidmi_gemm_f16_w4"]
         libs.append((os.path.basename(p), lib))
     rounds = int(sys.argv[2]) if len(sys.argv) > 2 else 2
     M = int(sys.argv[3]) if len(sys.argv) > 3 else 864256
