@@ -28,7 +28,8 @@ extern "C" {
 const char* reidmi_last_error(void);
 /* 4 since round 4: the A/B-only entry points (forced GEMM tiling, distance-kernel variant, the
  * fused QKV + attention kernel) moved to the tools library (include/reidmi_tools.h).
- * 5: reidmi_rr_jaccard_topk_rows / reidmi_rr_jaccard_topk_workspace_bytes added. */
+ * 5: reidmi_rr_jaccard_topk_rows / reidmi_rr_jaccard_topk_workspace_bytes added.
+ * 6: reidmi_search_merge_f32 added. */
 int reidmi_abi_version(void);
 
 /* ------------------------------------------------------------ retrieval back end */
@@ -92,6 +93,25 @@ int reidmi_search_f32(const float* q, int64_t Q, int64_t ldq, const float* g, in
                       int k, const int64_t* q_pids, const int64_t* q_cams, const int64_t* g_pids,
                       const int64_t* g_cams, int32_t* out_idx, float* out_dist, int64_t ldo, void* ws,
                       int64_t ws_bytes, void* stream);
+
+/* Joins S partial rank lists per query into one: the lists of a gallery searched in blocks, or
+ * on several GPUs a shard each.  List s of query i is in_idx[s*list_stride + i*ldi + 0..k_in) with
+ * in_dist laid out the same way: the rows reidmi_search_f32 writes over block s (ascending by
+ * (distance, index), ended by -1 / +inf padding; an entry is present iff its index >= 0).
+ * base: int64 [S], nullable (= all zero); the global index of an entry is base[s] + index and
+ * must fit int32.  out_idx[i*ldo + 0..k) / out_dist (nullable) are the k smallest present
+ * entries of the S lists, ascending by (distance, global index), padded with -1 / +inf: ties go
+ * by the global index, never by the order in which the lists are passed.  As a (query, item)
+ * distance does not depend on the block the item was in, merged block results are, bit for bit,
+ * reidmi_search_f32 over the concatenated gallery (given k_in >= min(k, the block's rows)).
+ * The caller guarantees that no global index occurs twice in a row's lists.
+ * 1 <= k <= 128, 1 <= k_in <= 128, S >= 1, S * k_in < 2^31, ldi >= k_in, ldo >= k,
+ * list_stride >= Q * ldi when S > 1; no relation between k and S * k_in is required.  The
+ * outputs must not overlap the inputs.  Q = 0 is a no-op.  No workspace, allocation or
+ * synchronisation. */
+int reidmi_search_merge_f32(const int32_t* in_idx, const float* in_dist, int S, int64_t Q, int k_in,
+                            int64_t list_stride, int64_t ldi, const int64_t* base, int k, int32_t* out_idx,
+                            float* out_dist, int64_t ldo, void* stream);
 
 /* Per-query part of eval_func — evaluate.py:40-80.  For query q: valid[q] (any match kept),
  * first[q] (0-based kept-rank of the first match), ap[q] (float64 AP exactly as numpy sums

@@ -16,4 +16,4 @@ REIDMI_API const char* reidmi_last_error(void) { return reidmi::g_err.c_str(); }
 // 4: the forced-variant entry points moved to libreidmi_tools.so (include/reidmi_tools.h);
 //    weight packing (reidmi_vit_weights_pack / reidmi_text_weights_pack);
 // 5: re-ranked rank lists (reidmi_rr_jaccard_topk_rows).
-REIDMI_API int reidmi_abi_version(void) { return 5; }
+REIDMI_API int reidmi_abi_version(void) { return 6; }

@@ -284,7 +284,7 @@ __global__ __launch_bounds__(256, DM2_MINWG) void search_f32_kernel(
     }
 }
 
-// Joins the S partial lists of one row (each sorted by (v, j), ranges ascending in j: select.h
+// Joins the S partial lists of one row (entries carry the gallery index j: select.h
 // topk_merge_dev).
 __global__ __launch_bounds__(256) void search_merge_kernel(const float2* __restrict__ lists, int64_t bands, int S,
                                                            int cap, int K, int32_t* __restrict__ out_idx,
@@ -293,6 +293,47 @@ __global__ __launch_bounds__(256) void search_merge_kernel(const float2* __restr
     const int64_t row = blockIdx.x, band = row / DM_BM, r = row % DM_BM;
     auto at = [&](int64_t p) { return lists[(((p / K) * bands + band) * DM_BM + r) * (int64_t)cap + p % K]; };
     topk_merge_dev(at, (int64_t)S * K, K, L, out_idx + row * ldo, out_dist ? out_dist + row * ldo : nullptr);
+}
+
+// reidmi_search_merge_f32: the same join over the rows reidmi_search_f32 writes (index and
+// distance arrays, list s of row i at s * list_stride + i * ldi), an entry's index moved by its
+// list's base to the global one.  One workgroup per query row, as search_merge_kernel: the S * k_in
+// entries are read once, coalesced, into TkLds and sorted there (DESIGN.md §5 on the choice).
+__global__ __launch_bounds__(256) void search_merge_lists_kernel(const int32_t* __restrict__ in_idx,
+                                                                 const float* __restrict__ in_dist, int S, int k_in,
+                                                                 int64_t list_stride, int64_t ldi,
+                                                                 const int64_t* __restrict__ base, int K,
+                                                                 int32_t* __restrict__ out_idx,
+                                                                 float* __restrict__ out_dist, int64_t ldo) {
+    __shared__ TkLds L;
+    const int64_t row = blockIdx.x;
+    auto at = [&](int64_t p) {
+        const int s = (int)p / k_in, e = (int)p - s * k_in;  // S * k_in < 2^31
+        const int64_t o = s * list_stride + row * ldi + e;
+        const int j = in_idx[o];
+        const int gj = j < 0 ? -1 : (int)((base ? base[s] : 0) + j);
+        return make_float2(in_dist[o], __int_as_float(gj));
+    };
+    topk_merge_dev(at, (int64_t)S * k_in, K, L, out_idx + row * ldo, out_dist ? out_dist + row * ldo : nullptr);
+}
+
+int search_merge_launch(const int32_t* in_idx, const float* in_dist, int S, int64_t Q, int k_in, int64_t list_stride,
+                        int64_t ldi, const int64_t* base, int k, int32_t* out_idx, float* out_dist, int64_t ldo,
+                        void* stream) {
+    RM_REQUIRE(k >= 1 && k <= SR_K_MAX, "search_merge: need 1 <= k <= 128");
+    RM_REQUIRE(k_in >= 1 && k_in <= SR_K_MAX, "search_merge: need 1 <= k_in <= 128");
+    RM_REQUIRE(S >= 1 && (int64_t)S * k_in < (1ll << 31), "search_merge: need S >= 1, S * k_in < 2^31");
+    RM_REQUIRE(Q >= 0 && Q < (1ll << 31), "search_merge: bad Q");
+    RM_REQUIRE(ldi >= k_in, "search_merge: ldi >= k_in");
+    RM_REQUIRE(ldo >= k, "search_merge: ldo >= k");
+    RM_REQUIRE(S == 1 || list_stride >= Q * ldi, "search_merge: list_stride >= Q * ldi (the lists overlap)");
+    RM_REQUIRE(in_idx != nullptr && in_dist != nullptr, "search_merge: in_idx and in_dist required");
+    RM_REQUIRE(out_idx != nullptr, "search_merge: out_idx required");
+    if (Q == 0) return OK;
+    hipLaunchKernelGGL(search_merge_lists_kernel, dim3((unsigned)Q), dim3(256), 0, (hipStream_t)stream, in_idx,
+                       in_dist, S, k_in, list_stride, ldi, base, k, out_idx, out_dist, ldo);
+    RM_LAUNCHED();
+    return OK;
 }
 
 // The launcher's choices, pure functions of the arguments: S gallery ranges of range_len columns
@@ -393,6 +434,12 @@ REIDMI_API int reidmi_search_f32(const float* q, int64_t Q, int64_t ldq, const f
                                  int64_t ldo, void* ws, int64_t ws_bytes, void* stream) {
     return search_impl(q, Q, ldq, g, G, ldg, D, k, q_pids, q_cams, g_pids, g_cams, out_idx, out_dist, ldo, ws,
                        ws_bytes, 0, 0, nullptr, stream);
+}
+
+REIDMI_API int reidmi_search_merge_f32(const int32_t* in_idx, const float* in_dist, int S, int64_t Q, int k_in,
+                                       int64_t list_stride, int64_t ldi, const int64_t* base, int k,
+                                       int32_t* out_idx, float* out_dist, int64_t ldo, void* stream) {
+    return search_merge_launch(in_idx, in_dist, S, Q, k_in, list_stride, ldi, base, k, out_idx, out_dist, ldo, stream);
 }
 
 #ifdef REIDMI_TOOLS

@@ -52,13 +52,18 @@ struct TkLds {
 };
 
 // The selection of one row by the whole workgroup: afterwards L.sv / L.si [0, min(K, cols))
-// hold the K smallest (val(j), j) in ascending (value, index) order among the j with
-// keep(v, j).  K <= TK_CAP - TK_CHUNK.
+// hold the K smallest (val(j), idx(j)) in ascending (value, index) order among the j with
+// keep(v, idx(j)).  idx(j) is the index the order and the result carry: the position j itself
+// (the default) or what position j of a list stands for; it must be unique among the kept j.
+// K <= TK_CAP - TK_CHUNK.
 struct KeepAll {
     __device__ bool operator()(float, int) const { return true; }
 };
-template <typename VAL, typename KEEP = KeepAll>
-__device__ inline void topk_row_dev(VAL val, int64_t cols, int K, TkLds& L, KEEP keep = KEEP{}) {
+struct IdxIsPos {
+    __device__ int operator()(int64_t j) const { return (int)j; }
+};
+template <typename VAL, typename KEEP = KeepAll, typename IDX = IdxIsPos>
+__device__ inline void topk_row_dev(VAL val, int64_t cols, int K, TkLds& L, KEEP keep = KEEP{}, IDX idx = IDX{}) {
     if (threadIdx.x == 0) { L.s_cnt = 0; L.s_nsel = 0; L.s_tv = __builtin_inff(); L.s_ti = 0x7fffffff; }
     __syncthreads();
     for (int64_t c0 = 0; c0 < cols; c0 += TK_CHUNK) {
@@ -69,10 +74,11 @@ __device__ inline void topk_row_dev(VAL val, int64_t cols, int K, TkLds& L, KEEP
             int64_t j = c0 + u * 256 + threadIdx.x;
             if (j < cols) {
                 const float v = val(j);
-                if (key_less(v, (int)j, tv, ti) && keep(v, (int)j)) {
+                const int ji = idx(j);
+                if (key_less(v, ji, tv, ti) && keep(v, ji)) {
                     int p = atomicAdd(&L.s_cnt, 1);
                     L.sv[nsel + p] = v;
-                    L.si[nsel + p] = (int)j;
+                    L.si[nsel + p] = ji;
                 }
             }
         }
@@ -101,17 +107,21 @@ __device__ inline void topk_row_dev(VAL val, int64_t cols, int K, TkLds& L, KEEP
 __device__ __forceinline__ int kv_idx(float2 e) { return __float_as_int(e.y); }
 
 // Joins the partial lists of one row by the whole workgroup: at(p), p < total, is entry p of
-// their concatenation.  Each list is sorted by (value, index) and the lists cover ascending
-// index ranges, so the order by (value, position) is the order by (value, index); padding
-// entries are skipped.  out_idx / out_dist (nullable) [K] get the K smallest, a short result
-// padded with -1 / +inf.
+// their concatenation, (value, the index it stands for); an entry with a negative index is
+// padding and is skipped.  The order is key_less on (value, that index), whatever the order of
+// the lists and of the entries inside them; the caller guarantees that no index occurs twice.
+// (Lists sorted by (value, index) over ascending index ranges, the fused kernels' own, come out
+// as they did under the order by position: the two orders agree there.)  out_idx / out_dist
+// (nullable) [K] get the K smallest, a short result padded with -1 / +inf; they are written
+// after the last at().
 template <typename AT>
 __device__ inline void topk_merge_dev(AT at, int64_t total, int K, TkLds& L, int32_t* __restrict__ out_idx,
                                       float* __restrict__ out_dist) {
-    topk_row_dev([&](int64_t p) { return at(p).x; }, total, K, L, [&](float, int p) { return kv_idx(at(p)) >= 0; });
+    topk_row_dev([&](int64_t p) { return at(p).x; }, total, K, L, [](float, int i) { return i >= 0; },
+                 [&](int64_t p) { return kv_idx(at(p)); });
     const int n = L.s_nsel;
     for (int t = threadIdx.x; t < K; t += blockDim.x) {
-        out_idx[t] = t < n ? kv_idx(at(L.si[t])) : -1;
+        out_idx[t] = t < n ? L.si[t] : -1;
         if (out_dist) out_dist[t] = t < n ? L.sv[t] : __builtin_inff();
     }
 }

@@ -22,6 +22,10 @@ semantics on whatever this process passed (a DDP script that evaluates on rank 0
 passes the full split on every rank, gets the single-process result and no hang):
   * R1_mAP_eval(..., sharded=True) / get_cmc_map(..., sharded=True): each rank passes ITS
     shard (its query rows, its gallery rows); every rank returns the CMC/mAP of the whole split.
+  * evaluate.search_sharded(...) and R1_mAP_eval(..., sharded=True).rank_lists(): the same shards
+    in; every rank searches all queries against its own gallery rows and the ranks exchange the
+    [Q][k] rank lists (gather_lists: Q * k * 8 bytes a rank), not the gallery features; every rank
+    returns the rank lists of the whole split.
   * re_ranking_device(..., sharded=True): every rank passes the FULL features; the stages are
     row-sharded over the ranks and every rank returns the whole (Q, G) matrix.
 Inside a default (unsharded) call, ``local()`` hides the process group from these helpers.
@@ -136,6 +140,20 @@ def gather_rows_var(x):
         dist.all_gather(bufs, pad)
         parts = [bufs[r][:ns[r]] for r in range(W)]
     return torch.cat(parts).to(x.device), ns
+
+
+def gather_lists(idx, dist, n_local):
+    """The exchange of the gallery-sharded search (evaluate.search_sharded_device): every rank holds
+    the [Q][k] rank list (idx int32, dist fp32) of all queries against ITS n_local gallery rows.
+    Returns (idx [W][Q][k], dist [W][Q][k] on idx's device, the shard offsets as a host int64 [W + 1]:
+    offsets[r] is the global index of rank r's gallery row 0, offsets[W] the gallery size).  One
+    all-gather of Q * k * 8 bytes per rank (index and distance bits in one int32 block) and one of
+    the sizes."""
+    both = torch.stack([idx, dist.view(torch.int32)])[None]  # [1][2][Q][k]
+    both, _ = gather_rows_var(both)
+    ns, _ = gather_rows_var(torch.tensor([n_local], dtype=torch.int64, device=idx.device))
+    offsets = torch.cat([torch.zeros(1, dtype=torch.int64), ns.cpu().cumsum(0)])
+    return both[:, 0], both[:, 1].view(torch.float32), offsets
 
 
 def all_to_all_var(send, in_splits):

@@ -98,19 +98,171 @@ def search_device(qf, gf, k, q_pids=None, q_camids=None, g_pids=None, g_camids=N
         raise _lib.ReidmiError("search: pass all four label arrays or none")
     qp, qc, gp, gc = (_as_dev_i64(a) for a in labels) if given else (None,) * 4
     k = int(k)
-    nb = _lib.load().reidmi_search_workspace_bytes(Q, G, D, k)
-    ws = torch.empty(max(nb, 16), device=qf.device, dtype=torch.uint8)
     idx = torch.empty((Q, max(k, 0)), device=qf.device, dtype=torch.int32)
     dist = torch.empty((Q, max(k, 0)), device=qf.device, dtype=torch.float32) if with_dist else None
-    _lib.call("reidmi_search_f32", _lib.ptr(qf), Q, qf.stride(0), _lib.ptr(gf), G, gf.stride(0), D, k, _lib.ptr(qp),
-              _lib.ptr(qc), _lib.ptr(gp), _lib.ptr(gc), _lib.ptr(idx), _lib.ptr(dist), max(k, 1), _lib.ptr(ws), nb,
-              _lib.stream())
+    _search_into(qf, gf, k, (qp, qc, gp, gc), idx, dist, max(k, 1))
     return idx, dist
+
+
+def _search_into(qf, gf, k, labels, idx, dist, ldo):
+    """reidmi_search_f32 of device features (and device labels, or four Nones) into rows of pitch ldo."""
+    Q, D = qf.shape
+    G = gf.shape[0]
+    nb = _lib.load().reidmi_search_workspace_bytes(Q, G, D, k)
+    ws = torch.empty(max(nb, 16), device=qf.device, dtype=torch.uint8)
+    _lib.call("reidmi_search_f32", _lib.ptr(qf), Q, qf.stride(0), _lib.ptr(gf), G, gf.stride(0), D, k,
+              *(_lib.ptr(a) for a in labels), _lib.ptr(idx), _lib.ptr(dist), ldo, _lib.ptr(ws), nb, _lib.stream())
 
 
 def search(qf, gf, k, q_pids=None, q_camids=None, g_pids=None, g_camids=None, with_dist=True):
     """search_device, returned as numpy arrays."""
     idx, dist = search_device(qf, gf, k, q_pids, q_camids, g_pids, g_camids, with_dist)
+    return idx.cpu().numpy(), (dist.cpu().numpy() if with_dist else None)
+
+
+def merge_lists_device(in_idx, in_dist, k, base=None, with_dist=True):
+    """Joins S partial rank lists per query (reidmi_search_merge_f32): in_idx int32 / in_dist fp32
+    [S][Q][k_in] device tensors of the same strides, rows as search_device writes them (padding -1 /
+    +inf); base: device int64 [S], the global index of list s's index 0 (None: all zero).  Returns
+    (idx int32 [Q][k], dist fp32 [Q][k] or None): the k smallest present entries by (distance, global
+    index), whatever the order of the lists."""
+    S, Q, k_in = in_idx.shape
+    if in_dist.shape != in_idx.shape or in_dist.stride() != in_idx.stride() or in_idx.stride(2) != 1:
+        raise _lib.ReidmiError("merge_lists: in_idx and in_dist must share one [S][Q][k_in] layout with unit entries")
+    _lib.require_cuda(in_idx, in_dist, base)
+    k = int(k)
+    idx = torch.empty((Q, max(k, 0)), device=in_idx.device, dtype=torch.int32)
+    dist = torch.empty((Q, max(k, 0)), device=in_idx.device, dtype=torch.float32) if with_dist else None
+    _lib.call("reidmi_search_merge_f32", _lib.ptr(in_idx), _lib.ptr(in_dist), S, Q, k_in, in_idx.stride(0),
+              in_idx.stride(1), _lib.ptr(base), k, _lib.ptr(idx), _lib.ptr(dist), max(k, 1), _lib.stream())
+    return idx, dist
+
+
+def _labels_given(what, *labels):
+    given = sum(a is not None for a in labels)
+    if given not in (0, len(labels)):
+        raise _lib.ReidmiError(f"{what}: pass all {len(labels)} label arrays or none")
+    return bool(given)
+
+
+class SearchAccumulator:
+    """search_device over a gallery that arrives in blocks: add() each block (a device or host
+    tensor, or a numpy array; a host block is on the device for the call only), then result().  Each
+    block is searched by reidmi_search_f32 and its list joined with the carried one by
+    reidmi_search_merge_f32 (S = 2, the block's indices moved by the number of items before it).  A
+    (query, item) distance does not depend on the block the item came in, and the join orders by
+    (distance, global index), so the result is bit for bit search_device(qf, torch.cat(blocks), k,
+    ...) for every way of cutting the gallery.  With q_pids / q_camids every block comes with its
+    g_pids / g_camids (evaluate.py:46-48's removal), without them none does.
+    Carried state: three [Q][k] lists of 8 bytes an entry (the carried one, the block's, the join's
+    output: the join never writes what it reads) and, during add(), the workspace of one block's
+    search; nothing grows with the gallery."""
+
+    def __init__(self, qf, k, q_pids=None, q_camids=None, with_dist=True):
+        self.qf = _as_dev_f32(qf)
+        self.k = int(k)
+        if not 1 <= self.k <= 128:
+            raise _lib.ReidmiError("SearchAccumulator: need 1 <= k <= 128")
+        self.labels = _labels_given("SearchAccumulator", q_pids, q_camids)
+        self.qp, self.qc = (_as_dev_i64(q_pids), _as_dev_i64(q_camids)) if self.labels else (None, None)
+        self.with_dist = with_dist
+        Q, dev = self.qf.shape[0], self.qf.device
+        # slot 1 takes each block's list; the carried list and the join's output alternate between 0 and 2
+        self._idx = torch.full((3, Q, self.k), -1, device=dev, dtype=torch.int32)
+        self._dist = torch.full((3, Q, self.k), float("inf"), device=dev, dtype=torch.float32)
+        self._carried = 0
+        self.count = 0  # gallery items added so far
+
+    def add(self, gf_block, g_pids=None, g_camids=None):
+        if _labels_given("SearchAccumulator.add", g_pids, g_camids) != self.labels:
+            raise _lib.ReidmiError("SearchAccumulator.add: gallery labels go with query labels: every block has "
+                                   "them or none has")
+        rows = int(gf_block.shape[0])
+        if rows == 0:
+            return
+        gf = _as_dev_f32(gf_block)
+        lab = (self.qp, self.qc, _as_dev_i64(g_pids), _as_dev_i64(g_camids)) if self.labels else (None,) * 4
+        if self.labels and (lab[2].numel() != rows or lab[3].numel() != rows):
+            raise _lib.ReidmiError("SearchAccumulator.add: one label per gallery row")
+        if self.count + rows >= 2 ** 31:
+            raise _lib.ReidmiError("SearchAccumulator: gallery indices must fit int32")
+        kb = min(self.k, rows)
+        slot = self._carried if self.count == 0 else 1
+        if kb < self.k:  # the search writes [0, kb) of a row
+            self._idx[slot].fill_(-1)
+            self._dist[slot].fill_(float("inf"))
+        _search_into(self.qf, gf, kb, lab, self._idx[slot], self._dist[slot], self.k)
+        if self.count:
+            c = self._carried
+            lo = min(c, 1)  # lists lo and lo + 1
+            base = torch.tensor([0, self.count] if c == 0 else [self.count, 0], dtype=torch.int64,
+                                device=self.qf.device)
+            Q, k = self.qf.shape[0], self.k
+            _lib.call("reidmi_search_merge_f32", _lib.ptr(self._idx[lo]), _lib.ptr(self._dist[lo]), 2, Q, k, Q * k, k,
+                      _lib.ptr(base), k, _lib.ptr(self._idx[2 - c]), _lib.ptr(self._dist[2 - c]), k, _lib.stream())
+            self._carried = 2 - c
+        self.count += rows
+
+    def result(self):
+        """(idx int32 [Q][k], dist fp32 [Q][k] or None) on the device, as search_device."""
+        if self.count < self.k:
+            raise _lib.ReidmiError(f"SearchAccumulator: need 1 <= k <= G, and {self.count} gallery items were added "
+                                   f"for k = {self.k}")
+        return self._idx[self._carried], (self._dist[self._carried] if self.with_dist else None)
+
+
+def search_blocks_device(qf, blocks, k, q_pids=None, q_camids=None, with_dist=True):
+    """SearchAccumulator over ``blocks``: an iterable of feature blocks or, with query labels, of
+    (features, g_pids, g_camids) tuples.  Bit for bit search_device over their concatenation."""
+    acc = SearchAccumulator(qf, k, q_pids, q_camids, with_dist)
+    for b in blocks:
+        acc.add(*b) if isinstance(b, (tuple, list)) else acc.add(b)
+    return acc.result()
+
+
+def search_blocks(qf, blocks, k, q_pids=None, q_camids=None, with_dist=True):
+    """search_blocks_device, returned as numpy arrays."""
+    idx, dist = search_blocks_device(qf, blocks, k, q_pids, q_camids, with_dist)
+    return idx.cpu().numpy(), (dist.cpu().numpy() if with_dist else None)
+
+
+def search_sharded_device(qf_local, gf_local, k, q_pids=None, q_camids=None, g_pids=None, g_camids=None,
+                          with_dist=True):
+    """search_device under R1_mAP_eval(sharded=True)'s contract (distributed.py): every rank passes
+    ITS query rows and ITS gallery rows (contiguous shards in rank order, labels likewise) and gets
+    the full (idx int32 [Q][k], dist fp32 [Q][k] or None), bit for bit the one-process search_device
+    over the rank-ordered concatenations.  The query features and labels are all-gathered, every rank
+    searches all queries against its own gallery shard, and the [Q][k] lists (8 bytes an entry) and
+    the shard sizes are all-gathered and joined by reidmi_search_merge_f32 with the shard offsets as
+    bases: gallery features never travel.  A shard of fewer than k rows, or none, contributes padded
+    rows.  Needs an initialised process group."""
+    from . import distributed as rd
+    if not rd._initialized():
+        raise _lib.ReidmiError("search_sharded needs an initialised torch.distributed process group")
+    labels = _labels_given("search_sharded", q_pids, q_camids, g_pids, g_camids)
+    qf_local, gf = _as_dev_f32(qf_local), _as_dev_f32(gf_local)
+    k = int(k)
+    if not 1 <= k <= 128:
+        raise _lib.ReidmiError("search_sharded: need 1 <= k <= 128")
+    qf, _ = rd.gather_rows_var(qf_local)
+    lab = (None,) * 4
+    if labels:
+        ql, _ = rd.gather_rows_var(torch.stack([_as_dev_i64(q_pids), _as_dev_i64(q_camids)], 1))
+        lab = (ql[:, 0].contiguous(), ql[:, 1].contiguous(), _as_dev_i64(g_pids), _as_dev_i64(g_camids))
+    Q, rows = qf.shape[0], gf.shape[0]
+    idx = torch.full((Q, k), -1, device=qf.device, dtype=torch.int32)
+    dist = torch.full((Q, k), float("inf"), device=qf.device, dtype=torch.float32)
+    if rows:
+        _search_into(qf, gf, min(k, rows), lab, idx, dist, k)
+    all_idx, all_dist, base = rd.gather_lists(idx, dist, rows)
+    if int(base[-1]) < k:
+        raise _lib.ReidmiError(f"search_sharded: need 1 <= k <= G, and the shards hold {int(base[-1])} gallery items")
+    return merge_lists_device(all_idx, all_dist, k, base[:-1].to(qf.device), with_dist)
+
+
+def search_sharded(qf_local, gf_local, k, q_pids=None, q_camids=None, g_pids=None, g_camids=None, with_dist=True):
+    """search_sharded_device, returned as numpy arrays."""
+    idx, dist = search_sharded_device(qf_local, gf_local, k, q_pids, q_camids, g_pids, g_camids, with_dist)
     return idx.cpu().numpy(), (dist.cpu().numpy() if with_dist else None)
 
 
@@ -260,8 +412,13 @@ class R1_mAP_eval():
         (evaluate.py:46-48; short rows end in -1 / +inf).  With ``reranking=True`` the lists are those
         of the k-reciprocal re-ranked distance compute() scores (k1 = 50, k2 = 15, lambda = 0.3;
         reranking.re_ranking_search, no (Q, G) matrix), dist the re-ranked distances; otherwise the
-        Euclidean neighbours (search).  1 <= k <= min(num_gallery, 128).  Single-process semantics on
-        this process's data (no sharded form)."""
+        Euclidean neighbours (search).  1 <= k <= min(num_gallery, 128).  ``sharded=False``:
+        single-process semantics on this process's data, no collective.  ``sharded=True`` (the shards
+        of compute()'s contract): every rank returns the lists of the whole split, all queries in rank
+        order against the rank-ordered gallery, bit for bit the single-process lists.  The Euclidean
+        lists come from search_sharded (every rank searches its own gallery shard, the ranks exchange
+        lists, not features); the re-ranked ones gather features and labels as compute() does (the
+        k-reciprocal stages need the whole gallery) and shard the rows (re_ranking_search(sharded=True))."""
         from . import distributed as rd
         feats = torch.cat(self.feats, dim=0)
         if self.feat_norm:
@@ -271,6 +428,20 @@ class R1_mAP_eval():
         if remove_same_cam:
             lab = (np.asarray(self.pids[:nq]), np.asarray(self.camids[:nq]), np.asarray(self.pids[nq:]),
                    np.asarray(self.camids[nq:]))
+        if self.sharded:
+            if not rd._initialized():
+                raise _lib.ReidmiError("R1_mAP_eval(sharded=True) needs an initialised torch.distributed process group")
+            if not self.reranking:
+                return search_sharded(feats[:nq], feats[nq:], k, *lab)
+            from .reranking import re_ranking_search
+            qf, _ = rd.gather_rows_var(feats[:nq].contiguous())
+            gf, _ = rd.gather_rows_var(feats[nq:].contiguous())
+            if remove_same_cam:
+                both = _as_dev_i64(np.stack([np.asarray(self.pids, np.int64), np.asarray(self.camids, np.int64)], 1))
+                ql, _ = rd.gather_rows_var(both[:nq].contiguous())
+                gl, _ = rd.gather_rows_var(both[nq:].contiguous())
+                lab = (ql[:, 0], ql[:, 1], gl[:, 0], gl[:, 1])
+            return re_ranking_search(qf, gf, k, 50, 15, 0.3, *lab, sharded=True)
         with rd.local():
             if self.reranking:
                 from .reranking import re_ranking_search
