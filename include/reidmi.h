@@ -29,7 +29,8 @@ const char* reidmi_last_error(void);
 /* 4 since round 4: the A/B-only entry points (forced GEMM tiling, distance-kernel variant, the
  * fused QKV + attention kernel) moved to the tools library (include/reidmi_tools.h).
  * 5: reidmi_rr_jaccard_topk_rows / reidmi_rr_jaccard_topk_workspace_bytes added.
- * 6: reidmi_search_merge_f32 added. */
+ * 6: reidmi_search_merge_f32 added.
+ * 7: reidmi_combine_rows_f32 added. */
 int reidmi_abi_version(void);
 
 /* ------------------------------------------------------------ retrieval back end */
@@ -305,6 +306,36 @@ int reidmi_rowmax_f32(const float* x, int64_t rows, int64_t cols, int64_t ldx, f
 int reidmi_nonzero_i32(const int32_t* flags, int64_t n, int32_t* idx, int32_t* count, void* stream);
 int reidmi_gather_rows_f32(const float* x, int64_t ldx, int64_t d, int64_t row0, const int32_t* idx, int64_t n,
                            float* out, int64_t ldo, void* stream);
+
+/* Weighted, indexed combination of feature rows, optionally L2-normalised: the device step of
+ * query expansion (q' = normalise(q + sum_i w_i g_nn_i)), database augmentation (the same for
+ * every gallery row against the gallery) and group pooling (multi-query, tracklets).
+ *   out[r] = f( base_w * base[r]  (if base),  { w[t] * src[idx[t]] : t in [offsets[r], offsets[r+1]) } )
+ * mode 0 sum, 1 mean, 2 max.  All fp32.  offsets: device int64 [rows + 1], ascending; idx: device
+ * int32; w: device fp32 or NULL (= 1).  Entries with idx < 0 are skipped (reidmi_search_f32's short
+ * rows end in -1).  Entries with idx >= n_src are skipped and counted in *bad (device int32,
+ * nullable; the caller zeroes it, the call adds).  base (nullable): [rows][ld_base].
+ * Arithmetic, fixed bit for bit (a plain float32 loop in this order is the exact oracle):
+ *   sum / mean: one fp32 accumulator per column, starting at base_w * base[r][c] (rounded), or +0
+ *     without a base; for each kept entry in list order acc = acc + (w[t] * src[j][c]), the product
+ *     rounded to fp32, then the sum rounded to fp32: never an FMA.  With w == NULL the term is
+ *     src[j][c] itself.  mean then divides by (float)(kept entries + (base ? 1 : 0)); a row with
+ *     nothing kept and no base is all +0.
+ *   max: the elementwise fmaxf over the base row (if any) and the kept rows; w must be NULL and
+ *     base_w is ignored; a row with nothing kept and no base is +0.
+ *   normalize != 0: the row is then normalised with reidmi_l2norm_f32's arithmetic (one device
+ *     definition, csrc/rownorm.h: the squared norm as one fmaf chain over the columns ascending,
+ *     each value divided by max(sqrt(ss), 1e-12)); the result equals reidmi_l2norm_f32 of the
+ *     normalize == 0 output bit for bit.
+ * Refused before any launch (REIDMI_EINVAL): a null src, offsets, idx or out when rows > 0;
+ * d <= 0, ld_src < d, ldo < d, ld_base < d with a base; mode outside 0..2; max given weights;
+ * n_src or rows >= 2^31.  rows == 0 is a no-op.  Any d, pitches and alignment (16-byte accesses
+ * when all pointers are 16-byte aligned and d and the pitches are multiples of 4).  out must not
+ * overlap src or base.  No workspace, allocation or synchronisation. */
+int reidmi_combine_rows_f32(const float* src, int64_t n_src, int64_t d, int64_t ld_src,
+                            const int64_t* offsets, const int32_t* idx, const float* w, int64_t rows,
+                            const float* base, int64_t ld_base, float base_w,
+                            int mode, int normalize, float* out, int64_t ldo, int32_t* bad, void* stream);
 
 /* ---------------------------------------------- multi-GPU exchange (RCCL, §8e) */
 

@@ -15,5 +15,7 @@ REIDMI_API const char* reidmi_last_error(void) { return reidmi::g_err.c_str(); }
 // 3: RCCL exchange (reidmi_comm_*); re-ranking without capacity limits;
 // 4: the forced-variant entry points moved to libreidmi_tools.so (include/reidmi_tools.h);
 //    weight packing (reidmi_vit_weights_pack / reidmi_text_weights_pack);
-// 5: re-ranked rank lists (reidmi_rr_jaccard_topk_rows).
-REIDMI_API int reidmi_abi_version(void) { return 6; }
+// 5: re-ranked rank lists (reidmi_rr_jaccard_topk_rows);
+// 6: merged rank lists (reidmi_search_merge_f32);
+// 7: combined feature rows (reidmi_combine_rows_f32).
+REIDMI_API int reidmi_abi_version(void) { return 7; }

@@ -9,6 +9,7 @@
 // distance.h, shared with search.hip; the kernels, their store epilogue and launchers are here.
 #include "backend.h"
 #include "distance.h"
+#include "rownorm.h"
 
 namespace reidmi {
 
@@ -28,7 +29,7 @@ __global__ __launch_bounds__(R) void row_sqnorm_kernel(const float* __restrict__
         if (i >= n) return;
         const float* r = x + i * ld;
         float acc = 0.0f;
-        for (int64_t k = 0; k < d; k++) acc = __builtin_fmaf(r[k], r[k], acc);
+        for (int64_t k = 0; k < d; k++) acc = l2_sq_step(acc, r[k]);
         out[i] = acc;
         return;
     }
@@ -58,12 +59,12 @@ __global__ __launch_bounds__(R) void row_sqnorm_kernel(const float* __restrict__
         __syncthreads();
         if (kt + 1 < nk) load((kt + 1) * RSQ_K);
 #pragma unroll
-        for (int k = 0; k < RSQ_K; k++) acc = __builtin_fmaf(tile[threadIdx.x][k], tile[threadIdx.x][k], acc);
+        for (int k = 0; k < RSQ_K; k++) acc = l2_sq_step(acc, tile[threadIdx.x][k]);
         __syncthreads();
     }
     if (i >= n) return;
     const float* r = x + i * ld;
-    for (int64_t k = nk * RSQ_K; k < d; k++) acc = __builtin_fmaf(r[k], r[k], acc);
+    for (int64_t k = nk * RSQ_K; k < d; k++) acc = l2_sq_step(acc, r[k]);
     out[i] = acc;
 }
 
@@ -72,13 +73,12 @@ void rows_sqnorm_launch(const float* x, int64_t n, int64_t d, int64_t ld, float*
                        out);
 }
 
-// y = x / max(sqrt(ss), 1e-12): one workgroup per row, coalesced.
+// y = x / max(sqrt(ss), 1e-12) (rownorm.h): one workgroup per row, coalesced.
 __global__ void row_scale_kernel(const float* __restrict__ x, const float* __restrict__ ss, int64_t d,
                                  int64_t ldx, float* __restrict__ y, int64_t ldy) {
     int64_t i = blockIdx.x;
-    float nrm = __builtin_sqrtf(ss[i]);
-    nrm = nrm < 1e-12f ? 1e-12f : nrm;
-    for (int64_t k = threadIdx.x; k < d; k += blockDim.x) y[i * ldy + k] = x[i * ldx + k] / nrm;
+    const float den = l2_denominator(ss[i]);
+    for (int64_t k = threadIdx.x; k < d; k += blockDim.x) y[i * ldy + k] = l2_scale(x[i * ldx + k], den);
 }
 
 // Store epilogue of the distance kernels.  SYM (the self-distance, q == g): also the mirrored tile.

@@ -7,6 +7,11 @@ and error behaviour, computed by libreidmi HIP kernels on the GPU.
                                    -> (cmc np.float32[max_rank], mAP np.float64)   evaluate.py:29-88
     R1_mAP_eval(num_query, max_rank=50, feat_norm=True, reranking=False)           evaluate.py:91-135
 
+Beyond the reference: ranked search (search, search_blocks, search_sharded), and the step
+between "the k nearest" and "the features I rank with" as one kernel (reidmi_combine_rows_f32):
+expand_features (AQE / alpha-QE), database_augmentation (DBA), pool_features (multi-query and
+tracklet pooling) and R1_mAP_eval(query_expansion=, db_augmentation=).
+
 The *_device variants keep everything on the GPU (torch tensors in, torch tensors out)
 and are what the fused pipeline (zero_shot_learning.py) uses.
 
@@ -266,6 +271,160 @@ def search_sharded(qf_local, gf_local, k, q_pids=None, q_camids=None, g_pids=Non
     return idx.cpu().numpy(), (dist.cpu().numpy() if with_dist else None)
 
 
+# ------------------------------------------- combined rows: query expansion, DBA, group pooling
+_COMBINE_MODES = {"sum": 0, "mean": 1, "max": 2}
+
+
+def _rows_f32(x, what):
+    """A 2-D fp32 device tensor with unit column stride; the row pitch is kept (no copy of a view
+    such as buf[:, :d])."""
+    if isinstance(x, np.ndarray):
+        x = torch.from_numpy(x)
+    x = x.to(device=_dev(), dtype=torch.float32)
+    if x.dim() != 2:
+        raise _lib.ReidmiError(f"combine_rows: {what} must be 2-D")
+    if x.shape[1] > 1 and x.stride(1) != 1 or x.shape[0] > 1 and x.stride(0) < x.shape[1]:
+        x = x.contiguous()
+    return x
+
+
+def _pitch(x):
+    return max(x.stride(0), x.shape[1]) if x.shape[0] > 1 else x.shape[1]
+
+
+def combine_rows_device(src, offsets, idx, w=None, base=None, base_w=1.0, mode="sum", normalize=False):
+    """out[r] = f(base_w * base[r], {w[t] * src[idx[t]] : offsets[r] <= t < offsets[r + 1]}), f = sum,
+    mean or max over the list, then optionally the L2 normalisation (reidmi_combine_rows_f32: one
+    kernel, no [rows][entries][D] intermediate).  src fp32 [n_src][D] and base fp32 [rows][D] or None
+    (unit column stride, any row pitch); offsets int64 [rows + 1] starting at 0, ascending, ending at
+    len(idx); idx int32; w fp32 like idx, or None (= 1; "max" takes none).  Entries < 0 are skipped
+    (search's padding); an entry >= n_src raises ReidmiError.  The arithmetic is fixed bit for bit
+    (include/reidmi.h): one fp32 accumulator per column, the entries added in list order, product
+    and sum each rounded, never fused; normalize=True equals l2_normalize_device of the
+    normalize=False result.  Returns fp32 [rows][D] on the device."""
+    if mode not in _COMBINE_MODES:
+        raise _lib.ReidmiError(f"combine_rows: mode must be 'sum', 'mean' or 'max', not {mode!r}")
+    src = _rows_f32(src, "src")
+    dev = src.device
+    offsets = _as_dev_i64(offsets).reshape(-1)
+    idx = (idx if isinstance(idx, torch.Tensor) else torch.from_numpy(np.asarray(idx)))
+    idx = idx.to(device=dev, dtype=torch.int32).reshape(-1).contiguous()
+    rows = offsets.numel() - 1
+    n_src, d = src.shape
+    if rows < 0:
+        raise _lib.ReidmiError("combine_rows: offsets needs rows + 1 entries")
+    if w is not None:
+        w = (w if isinstance(w, torch.Tensor) else torch.from_numpy(np.asarray(w)))
+        w = w.to(device=dev, dtype=torch.float32).reshape(-1).contiguous()
+        if w.numel() != idx.numel():
+            raise _lib.ReidmiError("combine_rows: one weight per list entry")
+    if base is not None:
+        base = _rows_f32(base, "base")
+        if tuple(base.shape) != (rows, d):
+            raise _lib.ReidmiError("combine_rows: base must be [rows][D]")
+    # the kernel trusts the offsets (they index idx): check them before it runs
+    if not bool(((offsets[0] == 0) & (offsets[-1] == idx.numel()) & (offsets[1:] >= offsets[:-1]).all()).item()):
+        raise _lib.ReidmiError("combine_rows: offsets must start at 0, ascend and end at len(idx)")
+    out = torch.empty((rows, d), device=dev, dtype=torch.float32)
+    bad = torch.zeros(1, device=dev, dtype=torch.int32)
+    _lib.call("reidmi_combine_rows_f32", _lib.ptr(src), n_src, d, _pitch(src), _lib.ptr(offsets), _lib.ptr(idx),
+              _lib.ptr(w), rows, _lib.ptr(base), 0 if base is None else _pitch(base), float(base_w),
+              _COMBINE_MODES[mode], int(bool(normalize)), _lib.ptr(out), d, _lib.ptr(bad), _lib.stream())
+    n_bad = int(bad.item())
+    if n_bad:
+        raise _lib.ReidmiError(f"combine_rows: {n_bad} list entries point past the {n_src} source rows")
+    return out
+
+
+def _alpha(alpha):
+    if isinstance(alpha, bool) or not isinstance(alpha, (int, np.integer)) or alpha < 0:
+        raise _lib.ReidmiError(f"expand_features: alpha must be an integer >= 0, not {alpha!r}")
+    return int(alpha)
+
+
+def expand_features_device(xf, gf, k, alpha=0, include_x=True):
+    """Query expansion: x' = normalise((x if include_x) + sum_i w_i g_nn_i) over the k nearest rows
+    of gf, nearest first (search_device(xf, gf, k) without labels: expansion never sees pids; ties by
+    gallery index).  alpha == 0: w_i = 1 (average query expansion, Chum et al.).  alpha >= 1 (an
+    integer): w_i = s_i ** alpha (alpha-QE, Radenovic et al.) with s = clamp(1 - dist / 2, 0), which
+    is the cosine when the rows are unit length (dist is the squared Euclidean distance, 2 - 2 cos);
+    the power is s multiplied by itself alpha - 1 times in fp32, left to right, no pow.  One
+    reidmi_combine_rows_f32 call on the lists (no [Q][k][D] tensor); fp32 [Q][D] on the device,
+    bit-reproducible.  1 <= k <= min(G, 128)."""
+    alpha = _alpha(alpha)
+    xf, gf = _as_dev_f32(xf), _as_dev_f32(gf)
+    idx, dist = search_device(xf, gf, k, with_dist=alpha > 0)
+    w = None
+    if alpha:
+        s = (1.0 - dist * 0.5).clamp_(min=0.0)
+        w = s
+        for _ in range(alpha - 1):
+            w = w * s
+    Q, k = idx.shape
+    offsets = torch.arange(Q + 1, device=xf.device, dtype=torch.int64) * k
+    return combine_rows_device(gf, offsets, idx, w, base=xf if include_x else None, base_w=1.0, mode="sum",
+                               normalize=True)
+
+
+def expand_features(xf, gf, k, alpha=0, include_x=True):
+    """expand_features_device, returned as a numpy array."""
+    return expand_features_device(xf, gf, k, alpha, include_x).cpu().numpy()
+
+
+def database_augmentation_device(gf, k, alpha=0):
+    """Database augmentation: every gallery row replaced by the normalised (weighted) sum of its k
+    nearest gallery rows, itself included once, through its own list (it is its own nearest row):
+    expand_features_device(gf, gf, k, alpha, include_x=False)."""
+    return expand_features_device(gf, gf, k, alpha, include_x=False)
+
+
+def database_augmentation(gf, k, alpha=0):
+    """database_augmentation_device, returned as a numpy array."""
+    return database_augmentation_device(gf, k, alpha).cpu().numpy()
+
+
+def multi_query_groups(pids, camids):
+    """The group key of Market-1501's multi-query protocol: one int64 key per (pid, camera), ordered
+    by pid, then camera (so np.unique's key order is that order)."""
+    pids = np.asarray(pids.cpu() if isinstance(pids, torch.Tensor) else pids, dtype=np.int64).reshape(-1)
+    cams = np.asarray(camids.cpu() if isinstance(camids, torch.Tensor) else camids, dtype=np.int64).reshape(-1)
+    if pids.shape != cams.shape:
+        raise _lib.ReidmiError("multi_query_groups: one camera per pid")
+    if cams.size == 0:
+        return pids.copy()
+    lo = cams.min()
+    return pids * (cams.max() - lo + 1) + (cams - lo)
+
+
+def pool_features_device(feat, groups, mode="mean", normalize=False):
+    """Pools the rows of feat that share a group key (multi-query crops of one (pid, camera):
+    multi_query_groups; tracklets: inference()'s seqs): (pooled fp32 [U][D] on the device, keys int64
+    [U], inverse int64 [n]; the last two numpy, as np.unique(groups, return_inverse=True) gives
+    them).  Row u pools the rows with key keys[u] in ascending row index; mode "mean", "sum" or
+    "max"; normalize: L2-normalise the pooled rows.  The lists (CSR) are built on the host, the
+    pooling is one reidmi_combine_rows_f32 call with the fixed arithmetic of combine_rows_device."""
+    feat = _rows_f32(feat, "feat")
+    groups = np.asarray(groups.cpu() if isinstance(groups, torch.Tensor) else groups).reshape(-1)
+    if groups.dtype.kind not in "iu":
+        raise _lib.ReidmiError("pool_features: groups must be integer keys")
+    groups = groups.astype(np.int64)
+    if groups.size != feat.shape[0]:
+        raise _lib.ReidmiError("pool_features: one group key per row")
+    keys, inverse, counts = np.unique(groups, return_inverse=True, return_counts=True)
+    inverse = inverse.reshape(-1).astype(np.int64)
+    offsets = np.zeros(len(keys) + 1, np.int64)
+    np.cumsum(counts, out=offsets[1:])
+    idx = np.argsort(inverse, kind="stable").astype(np.int32)
+    pooled = combine_rows_device(feat, offsets, idx, mode=mode, normalize=normalize)
+    return pooled, keys, inverse
+
+
+def pool_features(feat, groups, mode="mean", normalize=False):
+    """pool_features_device with the pooled rows returned as a numpy array."""
+    pooled, keys, inverse = pool_features_device(feat, groups, mode, normalize)
+    return pooled.cpu().numpy(), keys, inverse
+
+
 def eval_rows_device(dist, q_pids, g_pids, q_camids, g_camids):
     """Per-query (valid, first_match_rank, AP, n_kept) for eval_func (evaluate.py:40-80), any
     number of positives per query.  (valid = -1 / overflow = 1 were a capacity signal of older
@@ -352,15 +511,49 @@ class R1_mAP_eval():
     global query order: every rank returns the CMC/mAP of the single-process run over the
     rank-ordered concatenation of the shards, bit for bit (contiguous shards in rank order =
     the single-process order).  Default (``sharded=False``): the reference's single-process
-    semantics on this process's data, no collective even under a process group."""
+    semantics on this process's data, no collective even under a process group.
 
-    def __init__(self, num_query, max_rank=50, feat_norm=True, reranking=False, sharded=False):
+    ``query_expansion`` / ``db_augmentation``: None (the default: today's path, untouched) or
+    ``(k, alpha)``.  After the normalisation the gallery rows become
+    database_augmentation_device(gf, k, alpha) when db_augmentation is given, then the query rows
+    become expand_features_device(qf, gf, k, alpha) (against that gallery) when query_expansion is;
+    compute() and rank_lists() then proceed on those features exactly as without.  Not with
+    ``sharded=True`` (ReidmiError)."""
+
+    def __init__(self, num_query, max_rank=50, feat_norm=True, reranking=False, sharded=False,
+                 query_expansion=None, db_augmentation=None):
         super(R1_mAP_eval, self).__init__()
         self.num_query = num_query
         self.max_rank = max_rank
         self.feat_norm = feat_norm
         self.reranking = reranking
         self.sharded = sharded
+        self.query_expansion = query_expansion
+        self.db_augmentation = db_augmentation
+        self._check_expansion()
+
+    def _check_expansion(self):
+        if self.query_expansion is None and self.db_augmentation is None:
+            return False
+        if self.sharded:
+            raise _lib.ReidmiError("R1_mAP_eval: query_expansion / db_augmentation are not available with "
+                                   "sharded=True")
+        for name, v in (("query_expansion", self.query_expansion), ("db_augmentation", self.db_augmentation)):
+            if v is not None and (not isinstance(v, (tuple, list)) or len(v) != 2):
+                raise _lib.ReidmiError(f"R1_mAP_eval: {name} must be None or (k, alpha)")
+        return True
+
+    def _expand(self, feats):
+        """The features compute() / rank_lists() score: DBA on the gallery rows, then QE on the query
+        rows against that gallery (each when asked for); ``feats`` itself when neither is."""
+        if not self._check_expansion():
+            return feats
+        qf, gf = feats[:self.num_query], feats[self.num_query:]
+        if self.db_augmentation is not None:
+            gf = database_augmentation_device(gf, *self.db_augmentation)
+        if self.query_expansion is not None:
+            qf = expand_features_device(qf, gf, *self.query_expansion)
+        return torch.cat([qf, gf], dim=0)
 
     def reset(self):
         self.feats = []
@@ -375,6 +568,7 @@ class R1_mAP_eval():
 
     def compute(self):  # called after each epoch
         from . import distributed as rd
+        self._check_expansion()
         feats = torch.cat(self.feats, dim=0)
         if self.feat_norm:
             print("The test feature is normalized")
@@ -384,7 +578,7 @@ class R1_mAP_eval():
                 raise _lib.ReidmiError("R1_mAP_eval(sharded=True) needs an initialised torch.distributed process group")
             return self._compute_sharded(feats)
         with rd.local():
-            return self._compute_local(feats)
+            return self._compute_local(self._expand(feats))
 
     def _compute_local(self, feats):
         qf = feats[:self.num_query]
@@ -420,6 +614,7 @@ class R1_mAP_eval():
         lists, not features); the re-ranked ones gather features and labels as compute() does (the
         k-reciprocal stages need the whole gallery) and shard the rows (re_ranking_search(sharded=True))."""
         from . import distributed as rd
+        self._check_expansion()
         feats = torch.cat(self.feats, dim=0)
         if self.feat_norm:
             feats = l2_normalize_device(feats)
@@ -443,6 +638,7 @@ class R1_mAP_eval():
                 lab = (ql[:, 0], ql[:, 1], gl[:, 0], gl[:, 1])
             return re_ranking_search(qf, gf, k, 50, 15, 0.3, *lab, sharded=True)
         with rd.local():
+            feats = self._expand(feats)
             if self.reranking:
                 from .reranking import re_ranking_search
                 return re_ranking_search(feats[:nq], feats[nq:], k, 50, 15, 0.3, *lab)
