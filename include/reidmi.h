@@ -30,7 +30,8 @@ const char* reidmi_last_error(void);
  * fused QKV + attention kernel) moved to the tools library (include/reidmi_tools.h).
  * 5: reidmi_rr_jaccard_topk_rows / reidmi_rr_jaccard_topk_workspace_bytes added.
  * 6: reidmi_search_merge_f32 added.
- * 7: reidmi_combine_rows_f32 added. */
+ * 7: reidmi_combine_rows_f32 added.
+ * 8: reidmi_eval_feat_f32 and the reidmi_evf_* stages added. */
 int reidmi_abi_version(void);
 
 /* ------------------------------------------------------------ retrieval back end */
@@ -126,6 +127,76 @@ int reidmi_eval_rows(const float* dist, int64_t Q, int64_t G, int64_t ldd, const
 /* Device workspace bytes (16-byte aligned) for reidmi_eval_rows: the gallery labels packed
  * once per call and the scratch of a query with more positives than fit LDS (O(G)). */
 int64_t reidmi_eval_rows_workspace_bytes(int64_t G);
+
+/* Matrix-free scoring: reidmi_eval_rows' per-query results from the features, without the Q x G
+ * matrix.  On finite features valid / first / ap / nkept are, bit for bit, what reidmi_distmat_f32
+ * followed by reidmi_eval_rows gives on the same inputs, for any cut of the gallery into blocks
+ * or shards and any order in which they are processed.  A gallery item's key is (distance, global
+ * index), the distance reidmi_distmat_f32's; an item of the query's pid and camera is removed
+ * (evaluate.py:46-48); a match (the query's pid, another camera) has as kept-rank the number of
+ * kept items with a smaller key.  Two more outputs give mINP: last[q] (int64, the kept-rank of
+ * the last match, -1 without one) and npos[q] (int32, the number of matches).
+ *
+ * The state of a scoring run is caller-owned device memory for Q queries and a capacity `cap`,
+ * the most matches any query may have (the caller takes it from the labels):
+ *   pos       [Q][cap] 8-byte entries {fp32 distance, int32 global gallery index}
+ *   pos_cnt   int32 [Q]   matches met so far (it keeps counting past cap: such a query overflowed)
+ *   junk_cnt  int32 [Q]   removed items met so far
+ *   hist      int32 [Q][cap + 1]   hist[q][b]: kept items with exactly b matches before them
+ *   overflow  one int32
+ * The caller zeroes pos_cnt, junk_cnt, hist and overflow.  The stages, in this order:
+ *
+ * reidmi_evf_matches, once per gallery block (Gb rows, the first one global index `base`):
+ * appends every query's matches in the block to pos, each with its exact distance (the scalar
+ * fmaf chain the distance kernel is bit-equal to) and base + j, and adds the block's removed
+ * items to junk_cnt.  A query that would exceed cap sets *overflow = 1 and writes nothing past
+ * its row.  O(Q * Gb) label compares and O(matches * D) arithmetic: no second distance pass.
+ * reidmi_evf_append: appends the lists of another block set or rank (src, the same Q and cap;
+ * after an all-gather) to dst, dst_cnt += src_cnt, with the same overflow rule.
+ * reidmi_evf_sort: sorts every list ascending by key.  Keys are unique, so the result does not
+ * depend on the order of the appends.  Lists of up to 512 entries sort in LDS, longer ones in place.
+ * reidmi_evf_count, once per gallery block, after the sort: the distance tile of
+ * reidmi_search_f32 (same accepted D, pitches and alignments, four workgroups per CU); its
+ * epilogue drops removed items and everything after the row's last match (one compare against
+ * that key in LDS) and adds 1 to hist[i][b] for the rest, b = the number of the row's matches with
+ * a smaller key.  Integer atomics, so blocks and ranks may be counted in any order and their hist
+ * arrays summed.
+ * reidmi_evf_finish: per query, rank_t = (inclusive scan of hist up to t) - 1, nkept = G_total -
+ * junk_cnt, AP summed with n = nkept exactly as reidmi_eval_rows sums it.  A query whose pos_cnt
+ * exceeds cap gets valid = -1 (first = last = -1, ap = 0) and sets *overflow = 1.  hist is consumed
+ * (overwritten with the ranks).  last and npos are nullable.
+ *
+ * ws of matches / count: reidmi_evf_workspace_bytes(Q, Gb) bytes, 16-byte aligned (the squared
+ * norms).  Refused with REIDMI_EINVAL before any HIP call: a null required pointer, Q < 0, Gb / G
+ * / D <= 0 (Q = 0 is a no-op), cap < 1, a pitch < D, base < 0 or base + Gb >= 2^31, a short or
+ * misaligned workspace, a missing label array (all four are required).  No allocation or
+ * synchronisation inside. */
+int64_t reidmi_evf_workspace_bytes(int64_t Q, int64_t Gb);
+int reidmi_evf_matches(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t Gb, int64_t ldg, int64_t D,
+                       const int64_t* q_pids, const int64_t* q_cams, const int64_t* g_pids, const int64_t* g_cams,
+                       int64_t base, int cap, void* pos, int32_t* pos_cnt, int32_t* junk_cnt, int32_t* overflow,
+                       void* ws, int64_t ws_bytes, void* stream);
+int reidmi_evf_append(void* dst_pos, int32_t* dst_cnt, const void* src_pos, const int32_t* src_cnt, int64_t Q,
+                      int cap, int32_t* overflow, void* stream);
+int reidmi_evf_sort(void* pos, const int32_t* pos_cnt, int64_t Q, int cap, void* stream);
+int reidmi_evf_count(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t Gb, int64_t ldg, int64_t D,
+                     const int64_t* q_pids, const int64_t* q_cams, const int64_t* g_pids, const int64_t* g_cams,
+                     int64_t base, int cap, const void* pos, const int32_t* pos_cnt, int32_t* hist, void* ws,
+                     int64_t ws_bytes, void* stream);
+int reidmi_evf_finish(const int32_t* pos_cnt, int32_t* hist, const int32_t* junk_cnt, int64_t Q, int cap,
+                      int64_t G_total, int32_t* overflow, int32_t* valid, int64_t* first, int64_t* last,
+                      int32_t* npos, double* ap, int64_t* nkept, void* stream);
+
+/* The stages above in one call for a resident gallery: matches, sort, count, finish, the state
+ * inside ws (zeroed by the call, as is *overflow).  ws: reidmi_eval_feat_workspace_bytes(Q, G, D,
+ * cap) bytes, 16-byte aligned: the squared norms, Q * cap * 8 bytes of lists, Q * (cap + 1) * 4 of
+ * histogram and 8 * Q of counts; no Q x G term (negative on bad arguments). */
+int64_t reidmi_eval_feat_workspace_bytes(int64_t Q, int64_t G, int64_t D, int cap);
+int reidmi_eval_feat_f32(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G, int64_t ldg, int64_t D,
+                         const int64_t* q_pids, const int64_t* q_cams, const int64_t* g_pids,
+                         const int64_t* g_cams, int cap, int32_t* valid, int64_t* first, int64_t* last,
+                         int32_t* npos, double* ap, int64_t* nkept, int32_t* overflow, void* ws, int64_t ws_bytes,
+                         void* stream);
 
 
 /* k-reciprocal re-ranking — re_ranking(probFea, galFea, k1, k2, lambda_value) (reranking.py:29-100),

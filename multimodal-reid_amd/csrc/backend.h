@@ -1,6 +1,6 @@
 // backend.h — the retrieval back end's internal launchers that another source calls, grouped by
-// the file that defines them (internal, not part of the C ABI).  Callers: rerank.hip, and
-// search.hip for the row norms.
+// the file that defines them (internal, not part of the C ABI).  Callers: rerank.hip, search.hip
+// and evalfeat.hip for the row norms, evalfeat.hip for its last stage.
 #pragma once
 #include "common.h"
 
@@ -18,6 +18,11 @@ int distmat_pre_launch(const float* q, int64_t Q, int64_t ldq, const float* g, i
 // search.hip
 int topk_launch(const float* x, int64_t rows, int64_t cols, int64_t ldx, const float* row_div, int k,
                 int32_t* out_idx, float* out_val, int64_t ldo, hipStream_t s);
+
+// eval.hip (the last stage of evalfeat.hip: it uses eval.hip's AP summers)
+int evf_finish_launch(const int32_t* pos_cnt, int32_t* hist, const int32_t* junk_cnt, int64_t Q, int cap,
+                      int64_t G_total, int32_t* overflow, int32_t* valid, int64_t* first, int64_t* last,
+                      int32_t* npos, double* ap, int64_t* nkept, hipStream_t s);
 
 // prefilter.hip
 int rank_select_launch(float* dot, int64_t ldd, const float* feat, int64_t ldf, int D, const float* sqn,

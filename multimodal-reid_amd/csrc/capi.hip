@@ -18,4 +18,4 @@ REIDMI_API const char* reidmi_last_error(void) { return reidmi::g_err.c_str(); }
 // 5: re-ranked rank lists (reidmi_rr_jaccard_topk_rows);
 // 6: merged rank lists (reidmi_search_merge_f32);
 // 7: combined feature rows (reidmi_combine_rows_f32).
-REIDMI_API int reidmi_abi_version(void) { return 7; }
+REIDMI_API int reidmi_abi_version(void) { return 8; }

@@ -1,9 +1,11 @@
 // eval.hip — per-query CMC / AP of the CLIP-ReID eval path on gfx950.
 //
 //   reidmi_eval_rows       per-query CMC/AP of eval_func                evaluate.py:40-80
+//   evf_finish_launch      the same ranks and AP from evalfeat.hip's histogram
 //
 // Bit-exact with numpy's float64 pairwise sums (the three summers below); the (value, index)
 // order and the sort are select.h's.
+#include "backend.h"
 #include "common.h"
 #include "select.h"
 
@@ -777,6 +779,104 @@ __global__ __launch_bounds__(256) void eval_rows_kernel(
             if (flag[t]) eval_row_large(q0 + t, dist, G, ld, qp, gp, qc, gc, valid, first, ap, nkept, huge, L);
         __syncthreads();
     }
+}
+
+// ------------------------------------------------- the last stage of the matrix-free scoring
+// evalfeat.hip counted, per query, hist[b] = kept gallery items (the matches among them) with
+// exactly b matches before them, over every gallery block; removed items were never counted.  One
+// wave per query scans it into the kept-ranks, rank_t = sum_{b <= t} hist[b] - 1, and sums the AP
+// with the summers above exactly as the two eval_rows kernels do: up to EVW_MAXP matches with the
+// ranks in LDS (pairwise_tree_par / pairwise_tree_wave, eval_rows_wg_kernel's choice), more with
+// the ranks written over hist and pairwise_sparse (eval_row_large's).
+__global__ __launch_bounds__(64) void evf_finish_kernel(const int32_t* __restrict__ pos_cnt, int32_t* hist_all,
+                                                        const int32_t* __restrict__ junk_cnt, int cap,
+                                                        int64_t G_total, int32_t* __restrict__ overflow,
+                                                        int32_t* __restrict__ valid, int64_t* __restrict__ first,
+                                                        int64_t* __restrict__ last, int32_t* __restrict__ npos,
+                                                        double* __restrict__ ap, int64_t* __restrict__ nkept) {
+    __shared__ int rks[EVW_MAXP];
+    __shared__ uint32_t path[EVW_MAXP];
+    __shared__ int dep[EVW_MAXP];
+    __shared__ double tvals[AP_STACK];
+    __shared__ int tops[AP_STACK];
+    __shared__ PwFrame pw[PW_DEPTH];
+    const int lane = threadIdx.x;
+    const int64_t q = blockIdx.x;
+    const int m = pos_cnt[q];
+    const int64_t n = G_total - junk_cnt[q];
+    int32_t* hist = hist_all + q * ((int64_t)cap + 1);
+    if (m > cap || m == 0) {  // a list that did not fit; no match
+        if (lane == 0) {
+            valid[q] = m ? -1 : 0;
+            first[q] = -1;
+            ap[q] = 0.0;
+            nkept[q] = n;
+            if (last) last[q] = -1;
+            if (npos) npos[q] = m;
+            if (m) *overflow = 1;
+        }
+        return;
+    }
+    const bool lds = m <= EVW_MAXP;
+    int carry = 0;
+    for (int c0 = 0; c0 < m; c0 += 64) {
+        const int k = c0 + lane;
+        int v = k < m ? hist[k] : 0;
+#pragma unroll
+        for (int o = 1; o < 64; o <<= 1) {
+            const int t = __shfl_up(v, o, 64);
+            if (lane >= o) v += t;
+        }
+        const int incl = v + carry;
+        carry = __shfl(incl, 63, 64);
+        if (k < m) {
+            if (lds) rks[k] = incl - 1;
+            else hist[k] = incl - 1;
+        }
+    }
+    __syncthreads();  // one wave: the ranks are visible to every lane
+    double sum;
+    int64_t r0, rl;
+    if (lds) {
+        const int* rk = rks;
+        sum = m <= 64 ? pairwise_tree_par(lane < m ? rk[lane] : 0, rk,
+                                          [](int t, int r) { return (double)(t + 1) / (double)(r + 1); }, m, n)
+                      : pairwise_tree_wave(rk, [&](int t) { return (double)(t + 1) / (double)(rk[t] + 1); }, m, n,
+                                           path, dep, tvals, tops);
+        r0 = rk[0];
+        rl = rk[m - 1];
+    } else {
+        sum = 0.0;
+        if (lane == 0)
+            sum = pairwise_sparse([&](int t) { return (int64_t)hist[t]; },
+                                  [&](int t) { return (double)(t + 1) / (double)(hist[t] + 1); }, m, n, pw);
+        r0 = hist[0];
+        rl = hist[m - 1];
+    }
+    if (lane == 0) {
+        valid[q] = 1;
+        first[q] = r0;
+        ap[q] = sum / (double)m;
+        nkept[q] = n;
+        if (last) last[q] = rl;
+        if (npos) npos[q] = m;
+    }
+}
+
+int evf_finish_launch(const int32_t* pos_cnt, int32_t* hist, const int32_t* junk_cnt, int64_t Q, int cap,
+                      int64_t G_total, int32_t* overflow, int32_t* valid, int64_t* first, int64_t* last,
+                      int32_t* npos, double* ap, int64_t* nkept, hipStream_t s) {
+    RM_REQUIRE(Q >= 0 && Q < (1ll << 31) && G_total > 0 && G_total < (1ll << 31), "evf_finish: bad shape");
+    RM_REQUIRE(cap >= 1, "evf_finish: need cap >= 1");
+    RM_REQUIRE(pos_cnt != nullptr && hist != nullptr && junk_cnt != nullptr && overflow != nullptr,
+               "evf_finish: pos_cnt, hist, junk_cnt and overflow required");
+    RM_REQUIRE(valid != nullptr && first != nullptr && ap != nullptr && nkept != nullptr,
+               "evf_finish: valid, first, ap and nkept required");
+    if (Q == 0) return OK;
+    hipLaunchKernelGGL(evf_finish_kernel, dim3((unsigned)Q), dim3(64), 0, s, pos_cnt, hist, junk_cnt, cap, G_total,
+                       overflow, valid, first, last, npos, ap, nkept);
+    RM_LAUNCHED();
+    return OK;
 }
 
 }  // namespace reidmi

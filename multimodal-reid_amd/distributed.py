@@ -26,6 +26,10 @@ passes the full split on every rank, gets the single-process result and no hang)
     in; every rank searches all queries against its own gallery rows and the ranks exchange the
     [Q][k] rank lists (gather_lists: Q * k * 8 bytes a rank), not the gallery features; every rank
     returns the rank lists of the whole split.
+  * evaluate.eval_features_sharded(...) and R1_mAP_eval(..., sharded=True, matrix_free=True): the
+    same shards in; the ranks exchange every query's match list and sum their rank histograms
+    (Q * cap * 8 + Q * (cap + 2) * 4 bytes a rank), not the gallery features; every rank returns the
+    CMC/mAP of the whole split.
   * re_ranking_device(..., sharded=True): every rank passes the FULL features; the stages are
     row-sharded over the ranks and every rank returns the whole (Q, G) matrix.
 Inside a default (unsharded) call, ``local()`` hides the process group from these helpers.
@@ -154,6 +158,17 @@ def gather_lists(idx, dist, n_local):
     ns, _ = gather_rows_var(torch.tensor([n_local], dtype=torch.int64, device=idx.device))
     offsets = torch.cat([torch.zeros(1, dtype=torch.int64), ns.cpu().cumsum(0)])
     return both[:, 0], both[:, 1].view(torch.float32), offsets
+
+
+def all_reduce_sum(x):
+    """The element-wise sum of x over the ranks, on x's device (integer counts: the same bits on
+    every rank whatever the order).  evaluate.eval_features_sharded_device sums its histograms and
+    removed-item counts with it: Q * (cap + 2) * 4 bytes a rank."""
+    if not _initialized():
+        return x
+    buf = x.contiguous().to(_collective_device(x), copy=True)
+    dist.all_reduce(buf, op=dist.ReduceOp.SUM)
+    return buf.to(x.device)
 
 
 def all_to_all_var(send, in_splits):

@@ -10,7 +10,9 @@ and error behaviour, computed by libreidmi HIP kernels on the GPU.
 Beyond the reference: ranked search (search, search_blocks, search_sharded), and the step
 between "the k nearest" and "the features I rank with" as one kernel (reidmi_combine_rows_f32):
 expand_features (AQE / alpha-QE), database_augmentation (DBA), pool_features (multi-query and
-tracklet pooling) and R1_mAP_eval(query_expansion=, db_augmentation=).
+tracklet pooling) and R1_mAP_eval(query_expansion=, db_augmentation=); and scoring without the
+(Q, G) matrix (reidmi_eval_feat_f32 / reidmi_evf_*): eval_func_features, eval_features_blocks,
+eval_features_sharded, mean_inp and R1_mAP_eval(matrix_free=True).
 
 The *_device variants keep everything on the GPU (torch tensors in, torch tensors out)
 and are what the fused pipeline (zero_shot_learning.py) uses.
@@ -472,6 +474,237 @@ def aggregate_cmc_map(valid, first, ap, nkept, num_g, max_rank=50, overflow=None
     return cmc, mAP
 
 
+# ------------------------------------------------- matrix-free scoring (reidmi_evf_*)
+def _np_i64(x):
+    return np.asarray(x.cpu() if isinstance(x, torch.Tensor) else x, dtype=np.int64).reshape(-1)
+
+
+def _max_pid_count(g_pids):
+    """The most gallery items one pid has: no query can have more matches."""
+    g_pids = _np_i64(g_pids)
+    return int(np.unique(g_pids, return_counts=True)[1].max()) if g_pids.size else 1
+
+
+class _EvfState:
+    """The caller-owned state of a scoring run (include/reidmi.h): per query a list of up to cap
+    matches (8 bytes each), the counts, and the histogram the count stage fills."""
+
+    def __init__(self, Q, cap, dev):
+        self.Q, self.cap, self.dev = Q, max(int(cap), 1), dev
+        self.pos = torch.zeros((Q, self.cap), device=dev, dtype=torch.int64)
+        self.pos_cnt = torch.zeros(Q, device=dev, dtype=torch.int32)
+        self.junk_cnt = torch.zeros(Q, device=dev, dtype=torch.int32)
+        self.overflow = torch.zeros(1, device=dev, dtype=torch.int32)
+        self.hist = None
+
+    def grow(self, cap):
+        """Room for lists of `cap` entries (the lists met so far are kept)."""
+        if cap > self.cap:
+            pos = torch.zeros((self.Q, cap), device=self.dev, dtype=torch.int64)
+            pos[:, :self.cap] = self.pos
+            self.pos, self.cap = pos, cap
+
+    def _block(self, name, qf, lab, gf, base, tail):
+        Q, D = qf.shape
+        rows = gf.shape[0]
+        nb = _lib.load().reidmi_evf_workspace_bytes(Q, rows)
+        ws = torch.empty(max(nb, 16), device=self.dev, dtype=torch.uint8)
+        _lib.call(name, _lib.ptr(qf), Q, qf.stride(0), _lib.ptr(gf), rows, gf.stride(0), D,
+                  *(_lib.ptr(a) for a in lab), int(base), self.cap, _lib.ptr(self.pos), _lib.ptr(self.pos_cnt), *tail,
+                  _lib.ptr(ws), nb, _lib.stream())
+
+    def matches(self, qf, lab, gf, base):
+        self._block("reidmi_evf_matches", qf, lab, gf, base, (_lib.ptr(self.junk_cnt), _lib.ptr(self.overflow)))
+
+    def append(self, pos, pos_cnt):
+        _lib.call("reidmi_evf_append", _lib.ptr(self.pos), _lib.ptr(self.pos_cnt), _lib.ptr(pos), _lib.ptr(pos_cnt),
+                  self.Q, self.cap, _lib.ptr(self.overflow), _lib.stream())
+
+    def sort(self):
+        _lib.call("reidmi_evf_sort", _lib.ptr(self.pos), _lib.ptr(self.pos_cnt), self.Q, self.cap, _lib.stream())
+        self.hist = torch.zeros((self.Q, self.cap + 1), device=self.dev, dtype=torch.int32)
+
+    def count(self, qf, lab, gf, base):
+        self._block("reidmi_evf_count", qf, lab, gf, base, (_lib.ptr(self.hist),))
+
+    def finish(self, g_total):
+        Q, dev = self.Q, self.dev
+        valid = torch.empty(Q, device=dev, dtype=torch.int32)
+        first = torch.empty(Q, device=dev, dtype=torch.int64)
+        last = torch.empty(Q, device=dev, dtype=torch.int64)
+        npos = torch.empty(Q, device=dev, dtype=torch.int32)
+        ap = torch.empty(Q, device=dev, dtype=torch.float64)
+        nkept = torch.empty(Q, device=dev, dtype=torch.int64)
+        _lib.call("reidmi_evf_finish", _lib.ptr(self.pos_cnt), _lib.ptr(self.hist), _lib.ptr(self.junk_cnt), Q, self.cap,
+                  int(g_total), _lib.ptr(self.overflow), _lib.ptr(valid), _lib.ptr(first), _lib.ptr(last),
+                  _lib.ptr(npos), _lib.ptr(ap), _lib.ptr(nkept), _lib.stream())
+        return valid, first, last, npos, ap, nkept, self.overflow
+
+
+def eval_features_device(qf, gf, q_pids, g_pids, q_camids, g_camids, cap=None):
+    """eval_rows_device(euclidean_distance_device(qf, gf), ...) without the (Q, G) matrix
+    (reidmi_eval_feat_f32: the ranks are counted in the distance kernel's epilogue): device
+    (valid, first, last, npos, ap, nkept, overflow), valid / first / ap / nkept bit for bit those of
+    the two calls; last: the kept-rank of the last match (-1 without one), npos: the number of
+    matches (mean_inp).  cap: the capacity of a query's match list; None: the largest count of one
+    pid in the gallery (no query can overflow)."""
+    qf, gf = _as_dev_f32(qf), _as_dev_f32(gf)
+    Q, D = qf.shape
+    G = gf.shape[0]
+    cap = _max_pid_count(g_pids) if cap is None else int(cap)
+    qp, gp, qc, gc = (_as_dev_i64(a) for a in (q_pids, g_pids, q_camids, g_camids))
+    dev = qf.device
+    valid = torch.empty(Q, device=dev, dtype=torch.int32)
+    first = torch.empty(Q, device=dev, dtype=torch.int64)
+    last = torch.empty(Q, device=dev, dtype=torch.int64)
+    npos = torch.empty(Q, device=dev, dtype=torch.int32)
+    ap = torch.empty(Q, device=dev, dtype=torch.float64)
+    nkept = torch.empty(Q, device=dev, dtype=torch.int64)
+    overflow = torch.empty(1, device=dev, dtype=torch.int32)  # written by the call
+    nb = _lib.load().reidmi_eval_feat_workspace_bytes(Q, G, D, cap)
+    ws = torch.empty(max(nb, 16), device=dev, dtype=torch.uint8)
+    _lib.call("reidmi_eval_feat_f32", _lib.ptr(qf), Q, qf.stride(0), _lib.ptr(gf), G, gf.stride(0), D, _lib.ptr(qp),
+              _lib.ptr(qc), _lib.ptr(gp), _lib.ptr(gc), cap, _lib.ptr(valid), _lib.ptr(first), _lib.ptr(last),
+              _lib.ptr(npos), _lib.ptr(ap), _lib.ptr(nkept), _lib.ptr(overflow), _lib.ptr(ws), nb, _lib.stream())
+    return valid, first, last, npos, ap, nkept, overflow
+
+
+def _aggregate_features(res, num_g, max_rank):
+    valid, first, last, npos, ap, nkept, overflow = res
+    torch.cuda.current_stream().synchronize()
+    return aggregate_cmc_map(valid.cpu().numpy(), first.cpu().numpy(), ap.cpu().numpy(), nkept.cpu().numpy(), num_g,
+                             max_rank, overflow.cpu().numpy())
+
+
+def eval_func_features(qf, gf, q_pids, g_pids, q_camids, g_camids, max_rank=50):
+    """eval_func(euclidean_distance(qf, gf), q_pids, g_pids, q_camids, g_camids, max_rank) without the
+    (Q, G) matrix: the same (cmc, mAP) bit for bit, and the same errors."""
+    gf = _as_dev_f32(gf)
+    return _aggregate_features(eval_features_device(qf, gf, q_pids, g_pids, q_camids, g_camids), gf.shape[0],
+                               max_rank)
+
+
+def eval_features_blocks_device(qf, blocks, q_pids, q_camids):
+    """eval_features_device over a gallery that arrives in blocks: ``blocks`` is a re-iterable of
+    (gf_block, g_pids, g_camids), or a callable returning such an iterator.  It is walked twice,
+    the matches first (reidmi_evf_matches; the lists grow with the largest pid count met), then the
+    counts (reidmi_evf_count); a host block is on the device for its call only, so one block is
+    resident at a time.  Bit for bit eval_features_device over the concatenation, for every way of
+    cutting the gallery.  Returns (its seven tensors, the gallery size)."""
+    qf = _as_dev_f32(qf)
+    qp, qc = _as_dev_i64(q_pids), _as_dev_i64(q_camids)
+    walk = blocks if callable(blocks) else (lambda: iter(blocks))
+    st = _EvfState(qf.shape[0], 1, qf.device)
+    seen = {}
+    sizes = []
+
+    def block(b, base):
+        gf, gp, gc = b
+        if base + int(gf.shape[0]) >= 2 ** 31:
+            raise _lib.ReidmiError("eval_features_blocks: gallery indices must fit int32")
+        gf, gp, gc = _as_dev_f32(gf), _as_dev_i64(gp), _as_dev_i64(gc)
+        if gp.numel() != gf.shape[0] or gc.numel() != gf.shape[0]:
+            raise _lib.ReidmiError("eval_features_blocks: one label per gallery row")
+        return gf, (qp, qc, gp, gc)
+
+    base = 0
+    for b in walk():
+        rows = int(b[0].shape[0])
+        sizes.append(rows)
+        if rows == 0:
+            continue
+        for pid, n in zip(*np.unique(_np_i64(b[1]), return_counts=True)):
+            seen[int(pid)] = seen.get(int(pid), 0) + int(n)
+        st.grow(max(seen.values()))
+        gf, lab = block(b, base)
+        st.matches(qf, lab, gf, base)
+        base += rows
+    total = base
+    if total == 0:
+        raise _lib.ReidmiError("eval_features_blocks: the gallery is empty")
+    st.sort()
+    base = 0
+    for n, b in enumerate(walk()):
+        rows = int(b[0].shape[0])
+        if n >= len(sizes) or rows != sizes[n]:
+            raise _lib.ReidmiError("eval_features_blocks: the second walk over the blocks differs from the first")
+        if rows == 0:
+            continue
+        gf, lab = block(b, base)
+        st.count(qf, lab, gf, base)
+        base += rows
+    if base != total:
+        raise _lib.ReidmiError("eval_features_blocks: the second walk over the blocks differs from the first")
+    return st.finish(total), total
+
+
+def eval_features_blocks(qf, blocks, q_pids, q_camids, max_rank=50):
+    """eval_func_features over a gallery in blocks (eval_features_blocks_device): (cmc, mAP)."""
+    res, total = eval_features_blocks_device(qf, blocks, q_pids, q_camids)
+    return _aggregate_features(res, total, max_rank)
+
+
+def eval_features_sharded_device(qf_local, gf_local, q_pids, q_camids, g_pids, g_camids):
+    """eval_features_device under search_sharded's contract: every rank passes ITS query rows and ITS
+    gallery rows (contiguous shards in rank order, labels likewise).  The query features, the query
+    labels and the gallery pids (for the list capacity) are all-gathered; every rank collects all
+    queries' matches in its own shard; the lists ([Q][cap] entries of 8 bytes) and their counts are
+    all-gathered and appended; every rank counts its own shard; the histograms and removed-item
+    counts are sum-all-reduced, and every rank finishes all queries.  No gallery feature leaves its
+    rank.  Returns (the seven tensors of eval_features_device for all queries, the gallery size),
+    bit for bit the one-process result."""
+    from . import distributed as rd
+    if not rd._initialized():
+        raise _lib.ReidmiError("eval_features_sharded needs an initialised torch.distributed process group")
+    rank, W = rd.world()
+    qf_local, gf = _as_dev_f32(qf_local), _as_dev_f32(gf_local)
+    dev = gf.device
+    qf, _ = rd.gather_rows_var(qf_local)
+    ql, _ = rd.gather_rows_var(torch.stack([_as_dev_i64(q_pids), _as_dev_i64(q_camids)], 1))
+    gp, gc = _as_dev_i64(g_pids), _as_dev_i64(g_camids)
+    gp_all, ns = rd.gather_rows_var(gp)
+    total, base, rows = sum(ns), sum(ns[:rank]), gf.shape[0]
+    if total == 0:
+        raise _lib.ReidmiError("eval_features_sharded: the gallery is empty")
+    if total >= 2 ** 31:
+        raise _lib.ReidmiError("eval_features_sharded: gallery indices must fit int32")
+    lab = (ql[:, 0].contiguous(), ql[:, 1].contiguous(), gp, gc)
+    Q = qf.shape[0]
+    mine = _EvfState(Q, _max_pid_count(gp_all), dev)
+    if rows:
+        mine.matches(qf, lab, gf, base)
+    lists, _ = rd.gather_rows_var(mine.pos[None])
+    counts, _ = rd.gather_rows_var(mine.pos_cnt[None])
+    st = _EvfState(Q, mine.cap, dev)
+    for r in range(W):
+        st.append(lists[r].contiguous(), counts[r].contiguous())
+    st.junk_cnt = mine.junk_cnt
+    st.sort()
+    if rows:
+        st.count(qf, lab, gf, base)
+    st.hist = rd.all_reduce_sum(st.hist)
+    st.junk_cnt = rd.all_reduce_sum(st.junk_cnt)
+    return st.finish(total), total
+
+
+def eval_features_sharded(qf_local, gf_local, q_pids, q_camids, g_pids, g_camids, max_rank=50):
+    """eval_func_features over gallery shards (eval_features_sharded_device): every rank returns the
+    one-process (cmc, mAP) bit for bit."""
+    res, total = eval_features_sharded_device(qf_local, gf_local, q_pids, q_camids, g_pids, g_camids)
+    return _aggregate_features(res, total, max_rank)
+
+
+def mean_inp(valid, last, npos):
+    """mINP (Ye et al., "Deep Learning for Person Re-identification: A Survey and Outlook"): the
+    mean over the valid queries of npos / (last + 1) in float64, last the 0-based kept-rank of the
+    query's last match (eval_features_device's outputs)."""
+    valid, last, npos = (np.asarray(a.cpu() if isinstance(a, torch.Tensor) else a) for a in (valid, last, npos))
+    v = valid > 0
+    if not v.any():
+        raise _lib.ReidmiError("mean_inp: no valid query")
+    return np.mean(npos[v].astype(np.float64) / (last[v].astype(np.float64) + 1.0))
+
+
 # ------------------------------------------------------------ reference surface
 def euclidean_distance(qf, gf):
     """evaluate.py:7-13 — returns a numpy float32 (Q,G) matrix."""
@@ -518,10 +751,16 @@ class R1_mAP_eval():
     database_augmentation_device(gf, k, alpha) when db_augmentation is given, then the query rows
     become expand_features_device(qf, gf, k, alpha) (against that gallery) when query_expansion is;
     compute() and rank_lists() then proceed on those features exactly as without.  Not with
-    ``sharded=True`` (ReidmiError)."""
+    ``sharded=True`` (ReidmiError).
+
+    ``matrix_free=True`` (default False: today's paths, untouched): compute() scores from the
+    features without the (Q, G) distance matrix — eval_func_features locally (after the expansion
+    above), eval_features_sharded under ``sharded=True`` (the ranks exchange match lists and rank
+    histograms; no feature all-gather) — and returns the default's (cmc, mAP) bit for bit.  Not with
+    ``reranking=True`` (ReidmiError): the re-ranked distance has no feature form."""
 
     def __init__(self, num_query, max_rank=50, feat_norm=True, reranking=False, sharded=False,
-                 query_expansion=None, db_augmentation=None):
+                 query_expansion=None, db_augmentation=None, matrix_free=False):
         super(R1_mAP_eval, self).__init__()
         self.num_query = num_query
         self.max_rank = max_rank
@@ -530,7 +769,14 @@ class R1_mAP_eval():
         self.sharded = sharded
         self.query_expansion = query_expansion
         self.db_augmentation = db_augmentation
+        self.matrix_free = matrix_free
         self._check_expansion()
+        self._check_matrix_free()
+
+    def _check_matrix_free(self):
+        if self.matrix_free and self.reranking:
+            raise _lib.ReidmiError("R1_mAP_eval: matrix_free=True is not available with reranking=True (the "
+                                   "re-ranked distance has no feature form)")
 
     def _check_expansion(self):
         if self.query_expansion is None and self.db_augmentation is None:
@@ -569,6 +815,7 @@ class R1_mAP_eval():
     def compute(self):  # called after each epoch
         from . import distributed as rd
         self._check_expansion()
+        self._check_matrix_free()
         feats = torch.cat(self.feats, dim=0)
         if self.feat_norm:
             print("The test feature is normalized")
@@ -576,9 +823,24 @@ class R1_mAP_eval():
         if self.sharded:
             if not rd._initialized():
                 raise _lib.ReidmiError("R1_mAP_eval(sharded=True) needs an initialised torch.distributed process group")
+            if self.matrix_free:
+                return self._compute_matrix_free(feats, eval_features_sharded)
             return self._compute_sharded(feats)
         with rd.local():
+            if self.matrix_free:
+                return self._compute_matrix_free(self._expand(feats), eval_func_features)
             return self._compute_local(self._expand(feats))
+
+    def _compute_matrix_free(self, feats, score):
+        nq = self.num_query
+        pids, camids = np.asarray(self.pids), np.asarray(self.camids)
+        print('=> Computing DistMat with euclidean_distance')
+        if score is eval_func_features:
+            cmc, mAP = score(feats[:nq], feats[nq:], pids[:nq], pids[nq:], camids[:nq], camids[nq:])
+        else:
+            cmc, mAP = score(feats[:nq], feats[nq:], pids[:nq], camids[:nq], pids[nq:], camids[nq:])
+        self._print(cmc, mAP)
+        return cmc, mAP
 
     def _compute_local(self, feats):
         qf = feats[:self.num_query]
