@@ -31,7 +31,8 @@ const char* reidmi_last_error(void);
  * 5: reidmi_rr_jaccard_topk_rows / reidmi_rr_jaccard_topk_workspace_bytes added.
  * 6: reidmi_search_merge_f32 added.
  * 7: reidmi_combine_rows_f32 added.
- * 8: reidmi_eval_feat_f32 and the reidmi_evf_* stages added. */
+ * 8: reidmi_eval_feat_f32 and the reidmi_evf_* stages added.
+ * 9: reidmi_search_bounded_f32 added. */
 int reidmi_abi_version(void);
 
 /* ------------------------------------------------------------ retrieval back end */
@@ -95,6 +96,37 @@ int reidmi_search_f32(const float* q, int64_t Q, int64_t ldq, const float* g, in
                       int k, const int64_t* q_pids, const int64_t* q_cams, const int64_t* g_pids,
                       const int64_t* g_cams, int32_t* out_idx, float* out_dist, int64_t ldo, void* ws,
                       int64_t ws_bytes, void* stream);
+
+/* reidmi_search_f32 under a per-query bound: only admissible items are ranked, and a row with
+ * fewer than k of them is padded with -1 / +inf.  The bound is the initial value of the row's
+ * running threshold, so the epilogue filters against it from the first tile on: nothing
+ * inadmissible enters a candidate list (a gallery block that cannot improve a carried list costs
+ * its distance tiles and nothing else).
+ * Bound of query i: bd = bound_dist[i*ldb], bi = bound_idx[i*ldb] (device fp32 / int32; the pitch
+ * ldb lets a caller pass column k-1 of a carried [Q][k] list in place).
+ * Gallery item j, at the distance d reidmi_distmat_f32 gives, is admissible for query i iff it
+ * passes the label predicate and
+ *     d < bd,
+ *  or d == bd and bound_idx == NULL             (the inclusive radius form: d <= bd),
+ *  or d == bd and index_base + j < bi           (the strict key form: (d, index_base + j) before
+ *                                                (bd, bi) in the order of the rank lists).
+ * index_base places this gallery's item j at index_base + j in the bound's index space (the items
+ * searched before this block); out_idx stays local to this gallery, as reidmi_search_f32's, so the
+ * rows feed reidmi_search_merge_f32 with base = index_base as before.  bi = 2^31 - 1 admits every
+ * tie at bd (the radius form for that row alone); bi <= index_base admits none.
+ * Output: the min(k, admissible) smallest admissible items by (d, j), bit for bit what
+ * reidmi_distmat_f32 + that filter + a stable top-k give, then the padding.
+ * bound_dist = +inf admits every finite distance whatever bound_idx holds (a not-yet-full carried
+ * list: +inf / -1); a NaN or -inf bound_dist admits nothing.
+ * bound_dist == NULL: bound_idx must be NULL too, and the call is reidmi_search_f32 bit for bit.
+ * Refused: bound_idx without bound_dist; ldb < 1; index_base < 0 or index_base + G > 2^31 - 1; and
+ * whatever reidmi_search_f32 refuses: shapes, k, labels, alignments and the workspace
+ * (reidmi_search_workspace_bytes(Q, G, D, k)) are its own. */
+int reidmi_search_bounded_f32(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G, int64_t ldg,
+                              int64_t D, int k, const int64_t* q_pids, const int64_t* q_cams, const int64_t* g_pids,
+                              const int64_t* g_cams, const float* bound_dist, const int32_t* bound_idx, int64_t ldb,
+                              int64_t index_base, int32_t* out_idx, float* out_dist, int64_t ldo, void* ws,
+                              int64_t ws_bytes, void* stream);
 
 /* Joins S partial rank lists per query into one: the lists of a gallery searched in blocks, or
  * on several GPUs a shard each.  List s of query i is in_idx[s*list_stride + i*ldi + 0..k_in) with

@@ -17,5 +17,7 @@ REIDMI_API const char* reidmi_last_error(void) { return reidmi::g_err.c_str(); }
 //    weight packing (reidmi_vit_weights_pack / reidmi_text_weights_pack);
 // 5: re-ranked rank lists (reidmi_rr_jaccard_topk_rows);
 // 6: merged rank lists (reidmi_search_merge_f32);
-// 7: combined feature rows (reidmi_combine_rows_f32).
-REIDMI_API int reidmi_abi_version(void) { return 8; }
+// 7: combined feature rows (reidmi_combine_rows_f32);
+// 8: matrix-free evaluation (reidmi_eval_feat_f32, reidmi_evf_*);
+// 9: bounded search (reidmi_search_bounded_f32).
+REIDMI_API int reidmi_abi_version(void) { return 9; }

@@ -4,6 +4,9 @@
 //   reidmi_search_f32      the k nearest gallery rows per query, with   evaluate.py:7-13, 40, 46-48
 //                          eval_func's same-id same-camera removal,
 //                          without the Q x G matrix
+//   reidmi_search_bounded_f32  the same under a per-query bound (a radius, or the k-th key of a
+//                          list carried from earlier gallery blocks): the bound is the initial
+//                          threshold of the row, so the epilogue filters against it from tile one
 //
 // The distance tile is distance.h's (the distance kernels' bits), the selection select.h's.
 #include "backend.h"
@@ -73,7 +76,10 @@ int topk_launch(const float* x, int64_t rows, int64_t cols, int64_t ldx, const f
 // v = dm_value, so v below has the distance kernel's bits, and selects in the epilogue instead
 // of storing:
 //   * (v, j) is kept when j passes the label predicate and key_less(v, j, thr[row]); thr[row]
-//     is the row's current K-th key in LDS (none until K candidates were seen) and only falls;
+//     is the row's bound (none: +inf) until K candidates were seen, then its current K-th key, in
+//     LDS, and only falls; s_own says which of the two it is (a bounded row that collects K
+//     candidates must still compact once, so that its own K-th key replaces the bound; one with
+//     fewer keeps the bound to the end and its final compaction pads);
 //   * kept pairs are appended to the row's list of `cap` entries in the workspace (L2-resident:
 //     after the first tiles a row keeps about K / t of tile t's 128 columns);
 //   * between tiles a wave compacts those of its 32 rows that just reached K candidates or could
@@ -83,7 +89,7 @@ int topk_launch(const float* x, int64_t rows, int64_t cols, int64_t ldx, const f
 // workgroups.  After the last tile every row is compacted once more: list[0, K) is the range's
 // sorted partial result, padded with (+inf, -1).  search_merge_kernel joins the S partial lists
 // of a row.  LDS: 33 024 B of operand stages (reused as the compaction scratch, 4 waves x cap
-// x 8 B) + 2 KB of row state (+ 2 KB of query labels): four workgroups per CU, as the distance
+// x 8 B) + 2.5 KB of row state (+ 2 KB of query labels): four workgroups per CU, as the distance
 // kernel.
 constexpr int SR_K_MAX = 128, SR_CAP_MAX = 512 /* 4 waves x 512 x 8 B of scratch fit the stages */, SR_SLOTS = 1024 /* 256 CUs x DM2_MINWG */;
 constexpr int SR_SMEM = 2 * 2 * DM2_BK * DM2_LD;  // floats
@@ -92,10 +98,18 @@ static_assert(SR_SMEM >= 2 * DM_BK * (DM_BM + DM_PAD) && SR_SMEM >= 4 * SR_CAP_M
 struct SrLabels {
     const int64_t *qp, *qc, *gp, *gc;
 };
+// reidmi_search_bounded_f32's per-query bound: (dist[i * ld], idx[i * ld]), the index in the space
+// where this gallery's item j is base + j.  dist == nullptr: no bound; idx == nullptr: the
+// inclusive radius form.  Read once, in the kernel's prologue.
+struct SrBound {
+    const float* dist;
+    const int32_t* idx;
+    int64_t ld, base;
+};
 
 // One wave compacts one row: list[0, n) -> the min(n, K) smallest in ascending (v, j) order.
 __device__ __forceinline__ void sr_compact_row(float2* __restrict__ list, uint64_t* sc, int n, int K, bool last,
-                                               float* tv, int* ti, int* cnt, int lane) {
+                                               float* tv, int* ti, int* own, int* cnt, int lane) {
     // (v, j) as one unsigned 64-bit key in key_less order: the order-preserving image of v's bits
     // above j (v is never -0: it is a sum with qq + gg >= +0; NaN never passes the filter)
     for (int t = lane; t < n; t += 64) {
@@ -120,7 +134,10 @@ __device__ __forceinline__ void sr_compact_row(float2* __restrict__ list, uint64
     const int ns = n < K ? n : K;
     if (last)
         for (int t = ns + lane; t < K; t += 64) list[t] = make_float2(__builtin_inff(), __int_as_float(-1));
-    if (lane == 0) *cnt = ns;
+    if (lane == 0) {
+        *cnt = ns;
+        if (n >= K) *own = 1;  // rank K - 1 existed: (tv, ti) is now the row's own K-th key
+    }
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
     __builtin_amdgcn_wave_barrier();  // the scratch is free for the wave's next row
 }
@@ -129,10 +146,10 @@ template <bool PIPE, bool LABELS>
 __global__ __launch_bounds__(256, DM2_MINWG) void search_f32_kernel(
     const float* __restrict__ q, const float* __restrict__ g, const float* __restrict__ qq,
     const float* __restrict__ gg, int64_t Q, int64_t G, int64_t D, int64_t ldq, int64_t ldg, int K, SrLabels lab,
-    int64_t range_len, int cap, float2* __restrict__ lists, int32_t* __restrict__ stats) {
+    SrBound bnd, int64_t range_len, int cap, float2* __restrict__ lists, int32_t* __restrict__ stats) {
     __shared__ float smem[SR_SMEM];
     __shared__ float s_tv[DM_BM], s_qq[DM_BM];
-    __shared__ int s_ti[DM_BM], s_cnt[DM_BM];
+    __shared__ int s_ti[DM_BM], s_cnt[DM_BM], s_own[DM_BM];
     __shared__ int64_t s_qp[LABELS ? DM_BM : 1], s_qc[LABELS ? DM_BM : 1];
     const DmThread t = dm_thread();
     const int tid = t.tid, lane = t.lane, wid = t.wid, wm = t.wm, wn = t.wn;
@@ -145,8 +162,23 @@ __global__ __launch_bounds__(256, DM2_MINWG) void search_f32_kernel(
     float2* const mylists = lists + (split * bands + band) * DM_BM * (int64_t)cap;
     if (tid < DM_BM) {
         const bool in = bm + tid < Q;
-        s_tv[tid] = __builtin_inff();
-        s_ti[tid] = 0x7fffffff;  // no threshold yet
+        // The row's running threshold starts at its bound (none: (+inf, every index)), so the
+        // epilogue's compare filters against it from the first tile on.  The bound's index moves to
+        // this gallery's local j once, here: <= 0 says no local j ties in, > G (clamped to G, which
+        // no j reaches) that every tie is in, as in the radius form.  Whether the threshold is the
+        // row's own K-th key is s_own, not a value of s_ti.
+        float tv0 = __builtin_inff();
+        int ti0 = 0x7fffffff;
+        if (bnd.dist != nullptr && in) {
+            tv0 = bnd.dist[(bm + tid) * bnd.ld];
+            if (bnd.idx != nullptr) {
+                const int64_t l = (int64_t)bnd.idx[(bm + tid) * bnd.ld] - bnd.base;
+                ti0 = l <= 0 ? 0 : (l > G ? (int)G : (int)l);
+            }
+        }
+        s_tv[tid] = tv0;
+        s_ti[tid] = ti0;
+        s_own[tid] = 0;
         s_cnt[tid] = 0;
         s_qq[tid] = in ? qq[bm + tid] : 0.0f;
         if constexpr (LABELS) {
@@ -262,7 +294,7 @@ __global__ __launch_bounds__(256, DM2_MINWG) void search_f32_kernel(
             const int row = wid + 4 * (lane & 31);
             const int n = s_cnt[row];
             const bool over = n + DM_BN > cap;
-            const bool has_thr = s_ti[row] != 0x7fffffff;
+            const bool has_thr = s_own[row] != 0;  // a carried-in bound is a threshold, but not the row's own
             const bool need = lane < 32 && bm + row < Q && (last || over || (!has_thr && n >= K));
             if (need && over && has_thr && !last) compactions++;  // stats[0]: forced by a full list
             uint64_t m = __ballot(need);
@@ -271,8 +303,8 @@ __global__ __launch_bounds__(256, DM2_MINWG) void search_f32_kernel(
                 const int b = __ffsll((unsigned long long)m) - 1;
                 m &= m - 1;
                 const int rw = wid + 4 * b;
-                sr_compact_row(mylists + (int64_t)rw * cap, sc, s_cnt[rw], K, last, &s_tv[rw], &s_ti[rw], &s_cnt[rw],
-                               lane);
+                sr_compact_row(mylists + (int64_t)rw * cap, sc, s_cnt[rw], K, last, &s_tv[rw], &s_ti[rw], &s_own[rw],
+                               &s_cnt[rw], lane);
             }
         }
         __syncthreads();  // thresholds and counts of the next tile; the scratch is a stage again
@@ -370,8 +402,9 @@ static int64_t sr_ws_bytes(int64_t Q, int64_t G, const SrPlan& p) {
 
 int search_impl(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G, int64_t ldg, int64_t D, int k,
                 const int64_t* q_pids, const int64_t* q_cams, const int64_t* g_pids, const int64_t* g_cams,
-                int32_t* out_idx, float* out_dist, int64_t ldo, void* ws, int64_t ws_bytes, int splits, int cap,
-                int32_t* stats, void* stream) {
+                const float* bound_dist, const int32_t* bound_idx, int64_t ldb, int64_t index_base, int32_t* out_idx,
+                float* out_dist, int64_t ldo, void* ws, int64_t ws_bytes, int splits, int cap, int32_t* stats,
+                void* stream) {
     RM_REQUIRE(Q >= 0 && G > 0 && G < 0x7fffffff && D > 0 && ldq >= D && ldg >= D, "search: bad shape");
     RM_REQUIRE(k >= 1 && k <= G, "search: need 1 <= k <= G");
     RM_REQUIRE(k <= SR_K_MAX,
@@ -379,6 +412,10 @@ int search_impl(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t 
     RM_REQUIRE(out_idx != nullptr && ldo >= k, "search: out_idx required, ldo >= k");
     const int nlab = (q_pids != nullptr) + (q_cams != nullptr) + (g_pids != nullptr) + (g_cams != nullptr);
     RM_REQUIRE(nlab == 0 || nlab == 4, "search: pass all four label arrays or none");
+    RM_REQUIRE(bound_dist != nullptr || bound_idx == nullptr, "search: bound_idx needs bound_dist");
+    RM_REQUIRE(ldb >= 1, "search: need ldb >= 1");
+    RM_REQUIRE(index_base >= 0 && index_base + G <= 0x7fffffff,
+               "search: need index_base >= 0 and index_base + G <= 2^31 - 1");
     SrPlan p;
     RM_REQUIRE(sr_plan(Q, G, k, splits, cap, &p), "search: bad splits or list capacity (k + 128 <= cap <= 512)");
     RM_REQUIRE(ws != nullptr && ((uintptr_t)ws & 15) == 0 && ws_bytes >= sr_ws_bytes(Q, G, p),
@@ -394,11 +431,12 @@ int search_impl(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t 
     rows_sqnorm_launch(g, G, D, ldg, gg, s);
     RM_LAUNCHED();
     const SrLabels lab{q_pids, q_cams, g_pids, g_cams};
+    const SrBound bnd{bound_dist, bound_idx, ldb, index_base};
     const dim3 grid((unsigned)(p.bands * p.S));
     const bool pipe = dm2_ok(q, ldq, g, ldg, D);
 #define SR_LAUNCH(PIPE, LAB)                                                                                      \
     hipLaunchKernelGGL((search_f32_kernel<PIPE, LAB>), grid, dim3(256), 0, s, q, g, qq, gg, Q, G, D, ldq, ldg, k, \
-                       lab, p.range_len, p.cap, lists, stats)
+                       lab, bnd, p.range_len, p.cap, lists, stats)
     if (pipe) {
         if (nlab) SR_LAUNCH(true, true);
         else SR_LAUNCH(true, false);
@@ -432,8 +470,17 @@ REIDMI_API int reidmi_search_f32(const float* q, int64_t Q, int64_t ldq, const f
                                  int64_t D, int k, const int64_t* q_pids, const int64_t* q_cams,
                                  const int64_t* g_pids, const int64_t* g_cams, int32_t* out_idx, float* out_dist,
                                  int64_t ldo, void* ws, int64_t ws_bytes, void* stream) {
-    return search_impl(q, Q, ldq, g, G, ldg, D, k, q_pids, q_cams, g_pids, g_cams, out_idx, out_dist, ldo, ws,
-                       ws_bytes, 0, 0, nullptr, stream);
+    return search_impl(q, Q, ldq, g, G, ldg, D, k, q_pids, q_cams, g_pids, g_cams, nullptr, nullptr, 1, 0, out_idx,
+                       out_dist, ldo, ws, ws_bytes, 0, 0, nullptr, stream);
+}
+
+REIDMI_API int reidmi_search_bounded_f32(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G,
+                                         int64_t ldg, int64_t D, int k, const int64_t* q_pids, const int64_t* q_cams,
+                                         const int64_t* g_pids, const int64_t* g_cams, const float* bound_dist,
+                                         const int32_t* bound_idx, int64_t ldb, int64_t index_base, int32_t* out_idx,
+                                         float* out_dist, int64_t ldo, void* ws, int64_t ws_bytes, void* stream) {
+    return search_impl(q, Q, ldq, g, G, ldg, D, k, q_pids, q_cams, g_pids, g_cams, bound_dist, bound_idx, ldb,
+                       index_base, out_idx, out_dist, ldo, ws, ws_bytes, 0, 0, nullptr, stream);
 }
 
 REIDMI_API int reidmi_search_merge_f32(const int32_t* in_idx, const float* in_dist, int S, int64_t Q, int k_in,
@@ -455,7 +502,18 @@ REIDMI_API int reidmi_search_f32_ex(const float* q, int64_t Q, int64_t ldq, cons
                                     const int64_t* g_pids, const int64_t* g_cams, int32_t* out_idx, float* out_dist,
                                     int64_t ldo, void* ws, int64_t ws_bytes, int splits, int cap, int32_t* stats,
                                     void* stream) {
-    return search_impl(q, Q, ldq, g, G, ldg, D, k, q_pids, q_cams, g_pids, g_cams, out_idx, out_dist, ldo, ws,
-                       ws_bytes, splits, cap, stats, stream);
+    return search_impl(q, Q, ldq, g, G, ldg, D, k, q_pids, q_cams, g_pids, g_cams, nullptr, nullptr, 1, 0, out_idx,
+                       out_dist, ldo, ws, ws_bytes, splits, cap, stats, stream);
+}
+
+REIDMI_API int reidmi_search_bounded_f32_ex(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G,
+                                            int64_t ldg, int64_t D, int k, const int64_t* q_pids,
+                                            const int64_t* q_cams, const int64_t* g_pids, const int64_t* g_cams,
+                                            const float* bound_dist, const int32_t* bound_idx, int64_t ldb,
+                                            int64_t index_base, int32_t* out_idx, float* out_dist, int64_t ldo,
+                                            void* ws, int64_t ws_bytes, int splits, int cap, int32_t* stats,
+                                            void* stream) {
+    return search_impl(q, Q, ldq, g, G, ldg, D, k, q_pids, q_cams, g_pids, g_cams, bound_dist, bound_idx, ldb,
+                       index_base, out_idx, out_dist, ldo, ws, ws_bytes, splits, cap, stats, stream);
 }
 #endif

@@ -90,12 +90,38 @@ def topk_rows_device(x, k, row_div=None, with_values=False):
     return (idx, val) if with_values else idx
 
 
-def search_device(qf, gf, k, q_pids=None, q_camids=None, g_pids=None, g_camids=None, with_dist=True):
+def _max_dist_rows(what, max_dist, Q):
+    """max_dist as a host fp32 [Q] tensor (a number: the same radius for every query), or None.
+    Checked before anything touches the GPU."""
+    if max_dist is None:
+        return None
+    if isinstance(max_dist, torch.Tensor):
+        t = max_dist.detach()
+    else:
+        try:
+            t = torch.from_numpy(np.asarray(max_dist, dtype=np.float32))
+        except (TypeError, ValueError):
+            raise _lib.ReidmiError(f"{what}: max_dist must be a number or one number per query") from None
+    if t.dim() == 0:
+        return t.to(torch.float32).reshape(1).expand(Q)
+    if tuple(t.shape) != (Q,):
+        raise _lib.ReidmiError(f"{what}: max_dist must be a number or have shape [{Q}] (one radius per query), "
+                               f"not {list(t.shape)}")
+    return t.to(torch.float32)
+
+
+def search_device(qf, gf, k, q_pids=None, q_camids=None, g_pids=None, g_camids=None, with_dist=True, max_dist=None):
     """The k nearest gallery rows of every query row (reidmi_search_f32: the selection runs in the
     distance kernel's epilogue, no (Q,G) matrix): (idx int32 [Q][k], dist fp32 [Q][k] or None) on the
     GPU, bit for bit euclidean_distance_device + topk_rows_device.  With the four label arrays, gallery
     items of the query's pid and camera are skipped (evaluate.py:46-48) and short rows are padded with
-    -1 / +inf.  1 <= k <= min(G, 128)."""
+    -1 / +inf.  1 <= k <= min(G, 128).
+    max_dist (a number, or a [Q] array or tensor; default None: no limit, reidmi_search_f32 as ever):
+    only items at a distance <= max_dist of their query are ranked (reidmi_search_bounded_f32's radius
+    form: the limit is the kernel's first threshold, nothing is filtered afterwards).  Rows are padded
+    with -1 / +inf, so (idx >= 0).sum(1) is the number of hits, up to k; a query with nothing within
+    its radius gets an all-padded row.  A NaN or -inf radius admits nothing."""
+    tau = _max_dist_rows("search", max_dist, qf.shape[0])
     qf, gf = _as_dev_f32(qf), _as_dev_f32(gf)
     Q, D = qf.shape
     G = gf.shape[0]
@@ -107,23 +133,32 @@ def search_device(qf, gf, k, q_pids=None, q_camids=None, g_pids=None, g_camids=N
     k = int(k)
     idx = torch.empty((Q, max(k, 0)), device=qf.device, dtype=torch.int32)
     dist = torch.empty((Q, max(k, 0)), device=qf.device, dtype=torch.float32) if with_dist else None
-    _search_into(qf, gf, k, (qp, qc, gp, gc), idx, dist, max(k, 1))
+    bound = None if tau is None else (tau.to(qf.device).contiguous(), None, 1, 0)
+    _search_into(qf, gf, k, (qp, qc, gp, gc), idx, dist, max(k, 1), bound)
     return idx, dist
 
 
-def _search_into(qf, gf, k, labels, idx, dist, ldo):
-    """reidmi_search_f32 of device features (and device labels, or four Nones) into rows of pitch ldo."""
+def _search_into(qf, gf, k, labels, idx, dist, ldo, bound=None):
+    """reidmi_search_f32 of device features (and device labels, or four Nones) into rows of pitch ldo.
+    bound: None, or reidmi_search_bounded_f32's (bound_dist, bound_idx or None, ldb, index_base), the
+    first two device tensors (or views) whose element i * ldb belongs to query i."""
     Q, D = qf.shape
     G = gf.shape[0]
     nb = _lib.load().reidmi_search_workspace_bytes(Q, G, D, k)
     ws = torch.empty(max(nb, 16), device=qf.device, dtype=torch.uint8)
-    _lib.call("reidmi_search_f32", _lib.ptr(qf), Q, qf.stride(0), _lib.ptr(gf), G, gf.stride(0), D, k,
-              *(_lib.ptr(a) for a in labels), _lib.ptr(idx), _lib.ptr(dist), ldo, _lib.ptr(ws), nb, _lib.stream())
+    if bound is None:
+        _lib.call("reidmi_search_f32", _lib.ptr(qf), Q, qf.stride(0), _lib.ptr(gf), G, gf.stride(0), D, k,
+                  *(_lib.ptr(a) for a in labels), _lib.ptr(idx), _lib.ptr(dist), ldo, _lib.ptr(ws), nb, _lib.stream())
+        return
+    bd, bi, ldb, base = bound
+    _lib.call("reidmi_search_bounded_f32", _lib.ptr(qf), Q, qf.stride(0), _lib.ptr(gf), G, gf.stride(0), D, k,
+              *(_lib.ptr(a) for a in labels), _lib.ptr(bd), _lib.ptr(bi), ldb, base, _lib.ptr(idx), _lib.ptr(dist),
+              ldo, _lib.ptr(ws), nb, _lib.stream())
 
 
-def search(qf, gf, k, q_pids=None, q_camids=None, g_pids=None, g_camids=None, with_dist=True):
+def search(qf, gf, k, q_pids=None, q_camids=None, g_pids=None, g_camids=None, with_dist=True, max_dist=None):
     """search_device, returned as numpy arrays."""
-    idx, dist = search_device(qf, gf, k, q_pids, q_camids, g_pids, g_camids, with_dist)
+    idx, dist = search_device(qf, gf, k, q_pids, q_camids, g_pids, g_camids, with_dist, max_dist)
     return idx.cpu().numpy(), (dist.cpu().numpy() if with_dist else None)
 
 
@@ -152,6 +187,12 @@ def _labels_given(what, *labels):
     return bool(given)
 
 
+# carry_bound's default in SearchAccumulator / search_blocks.  On: at 10 000 x 1 000 000, D = 1792 it was
+# no slower at any measured row (1 / 8 / 64 blocks, k = 10 and 128: 1.00 / 0.93 / 0.79 and 1.00 / 0.69 /
+# 0.38 of the time without it; DESIGN.md §5, profiles/search_blocks_carry_bench.txt).
+CARRY_BOUND_DEFAULT = True
+
+
 class SearchAccumulator:
     """search_device over a gallery that arrives in blocks: add() each block (a device or host
     tensor, or a numpy array; a host block is on the device for the call only), then result().  Each
@@ -163,10 +204,28 @@ class SearchAccumulator:
     g_pids / g_camids (evaluate.py:46-48's removal), without them none does.
     Carried state: three [Q][k] lists of 8 bytes an entry (the carried one, the block's, the join's
     output: the join never writes what it reads) and, during add(), the workspace of one block's
-    search; nothing grows with the gallery."""
+    search; nothing grows with the gallery.
+    carry_bound: from the second block on, search each block under the carried list's k-th key
+    (reidmi_search_bounded_f32's key form: column k-1 of the carried list in place, index_base = the
+    items before the block), so that a block's workgroups start with the threshold the earlier blocks
+    reached and append only what can enter the carried list; a not-yet-full row holds +inf / -1 there,
+    which admits everything.  The join and the result are the same either way.  Default True: measured
+    no slower at any row of DESIGN.md §5's table and up to 2.6 times faster (64 blocks, k = 128);
+    False searches every block unbounded, as before the bounded search existed.
+    max_dist (a number or one per query): only items within that distance of their query are ranked,
+    rows padded with -1 / +inf as search_device(max_dist=) pads them.  It bounds the first block (the
+    radius form) and, with carry_bound, every row whose carried list is not yet full; a full row's
+    k-th key is at or below the radius, so it is the tighter bound and takes over.  No block is ever
+    searched under a bound that admits more than the radius."""
 
-    def __init__(self, qf, k, q_pids=None, q_camids=None, with_dist=True):
+    def __init__(self, qf, k, q_pids=None, q_camids=None, with_dist=True, carry_bound=CARRY_BOUND_DEFAULT,
+                 max_dist=None):
+        if not isinstance(carry_bound, (bool, np.bool_)):
+            raise _lib.ReidmiError("SearchAccumulator: carry_bound must be True or False")
+        tau = _max_dist_rows("SearchAccumulator", max_dist, qf.shape[0])
+        self.carry_bound = bool(carry_bound)
         self.qf = _as_dev_f32(qf)
+        self._tau = None if tau is None else tau.to(self.qf.device).contiguous()
         self.k = int(k)
         if not 1 <= self.k <= 128:
             raise _lib.ReidmiError("SearchAccumulator: need 1 <= k <= 128")
@@ -198,7 +257,7 @@ class SearchAccumulator:
         if kb < self.k:  # the search writes [0, kb) of a row
             self._idx[slot].fill_(-1)
             self._dist[slot].fill_(float("inf"))
-        _search_into(self.qf, gf, kb, lab, self._idx[slot], self._dist[slot], self.k)
+        _search_into(self.qf, gf, kb, lab, self._idx[slot], self._dist[slot], self.k, self._bound())
         if self.count:
             c = self._carried
             lo = min(c, 1)  # lists lo and lo + 1
@@ -210,6 +269,18 @@ class SearchAccumulator:
             self._carried = 2 - c
         self.count += rows
 
+    def _bound(self):
+        """The next block's bound for _search_into: the carried k-th key and / or the radius."""
+        k = self.k
+        if self.count == 0 or not self.carry_bound:
+            return None if self._tau is None else (self._tau, None, 1, self.count)
+        bd, bi = self._dist[self._carried][:, k - 1], self._idx[self._carried][:, k - 1]
+        if self._tau is None:
+            return bd, bi, k, self.count
+        full = bi >= 0  # else the radius, with every tie at it in: no index reaches 2^31 - 1
+        return (torch.where(full, bd, self._tau), torch.where(full, bi, torch.full_like(bi, 2 ** 31 - 1)), 1,
+                self.count)
+
     def result(self):
         """(idx int32 [Q][k], dist fp32 [Q][k] or None) on the device, as search_device."""
         if self.count < self.k:
@@ -218,18 +289,21 @@ class SearchAccumulator:
         return self._idx[self._carried], (self._dist[self._carried] if self.with_dist else None)
 
 
-def search_blocks_device(qf, blocks, k, q_pids=None, q_camids=None, with_dist=True):
+def search_blocks_device(qf, blocks, k, q_pids=None, q_camids=None, with_dist=True,
+                         carry_bound=CARRY_BOUND_DEFAULT, max_dist=None):
     """SearchAccumulator over ``blocks``: an iterable of feature blocks or, with query labels, of
-    (features, g_pids, g_camids) tuples.  Bit for bit search_device over their concatenation."""
-    acc = SearchAccumulator(qf, k, q_pids, q_camids, with_dist)
+    (features, g_pids, g_camids) tuples.  Bit for bit search_device over their concatenation (with
+    the same max_dist), whatever carry_bound is."""
+    acc = SearchAccumulator(qf, k, q_pids, q_camids, with_dist, carry_bound, max_dist)
     for b in blocks:
         acc.add(*b) if isinstance(b, (tuple, list)) else acc.add(b)
     return acc.result()
 
 
-def search_blocks(qf, blocks, k, q_pids=None, q_camids=None, with_dist=True):
+def search_blocks(qf, blocks, k, q_pids=None, q_camids=None, with_dist=True, carry_bound=CARRY_BOUND_DEFAULT,
+                  max_dist=None):
     """search_blocks_device, returned as numpy arrays."""
-    idx, dist = search_blocks_device(qf, blocks, k, q_pids, q_camids, with_dist)
+    idx, dist = search_blocks_device(qf, blocks, k, q_pids, q_camids, with_dist, carry_bound, max_dist)
     return idx.cpu().numpy(), (dist.cpu().numpy() if with_dist else None)
 
 

@@ -1,7 +1,9 @@
 """Blocked search against the one-call search, in one process:
 
     one-call   evaluate.search_device(qf, gf, k)                       (the baseline)
-    blocked    evaluate.search_blocks_device(qf, B equal blocks of gf, k), for every B asked for
+    blocked    evaluate.search_blocks_device(qf, B equal blocks of gf, k, carry_bound=False) and
+               the same with carry_bound=True (every block after the first searched under the
+               carried list's k-th key, reidmi_search_bounded_f32), for every B asked for
 
 on identity-clustered, L2-normalised features drawn on the device (synthetic.features'
 construction), the gallery resident: the blocks are views of it, so the difference is what the
@@ -70,7 +72,8 @@ def run(q, g, k, blocks, reps, out):
     G = g.shape[0]
     variants = {"one_call": lambda: evaluate.search_device(q, g, k)}
     for B in blocks:
-        variants[f"blocks_{B}"] = lambda B=B: evaluate.search_blocks_device(q, cut(g, B), k)
+        variants[f"blocks_{B}"] = lambda B=B: evaluate.search_blocks_device(q, cut(g, B), k, carry_bound=False)
+        variants[f"blocks_{B}_carry"] = lambda B=B: evaluate.search_blocks_device(q, cut(g, B), k, carry_bound=True)
     want = None
     t, peak = {n: [] for n in variants}, {}
     for name, fn in variants.items():  # warm, and equal before anything is timed
@@ -91,7 +94,10 @@ def run(q, g, k, blocks, reps, out):
         if name != "one_call":
             B = int(name.split("_")[1])
             rec[name + "_time_over_one_call"] = round(min(t[name]) / base, 3)
-            rec[name + "_block_bytes"] = 4 * D * -(-G // B)
+            if name.endswith("_carry"):
+                rec[name + "_time_over_no_carry"] = round(min(t[name]) / min(t[name[:-6]]), 3)
+            else:
+                rec[name + "_block_bytes"] = 4 * D * -(-G // B)
     # one block's join alone (reidmi_search_merge_f32, S = 2): the result beside itself moved by G
     two = (torch.stack([want[0], want[0]]), torch.stack([want[1], want[1]]))
     base = torch.tensor([0, G], dtype=torch.int64, device="cuda")
@@ -120,7 +126,8 @@ def main():
     q, g = features(a.Q, a.G, a.D, a.ids, 7)
     with open(a.out, "w") as out:
         out.write(f"# tools/search_blocks_bench.py on {torch.cuda.get_device_name(0)}: evaluate.search_device against "
-                  "search_blocks_device over equal blocks of the resident gallery; HIP events, warm, alternating\n")
+                  "search_blocks_device over equal blocks of the resident gallery, carry_bound off and on; HIP events, "
+                  "warm, alternating\n")
         for k in (int(v) for v in a.ks.split(",")):
             run(q, g, k, [int(v) for v in a.blocks.split(",")], a.reps, out)
 
