@@ -296,7 +296,7 @@ int reidmi_rr_rank_rows_f16(const float* feat, int64_t N, int64_t D, int64_t ldf
  * streaming selection) at any N; S >= 2 = the selection inside the GEMM's epilogue against
  * per-row thresholds from every S-th item (prefilter.hip "R2 pre-filter with the selection in the
  * GEMM"), when floor(N / S) spans at least one 256-column tile and 4 K items (else the dense
- * form).  Same output bits.  reidmi_rr_rank_rows_f16 uses S = 16 (rerank.hip RR_SAMPLE_STRIDE):
+ * form).  Same output bits.  reidmi_rr_rank_rows_f16 uses S = 16 (rerank_rank.hip RR_SAMPLE_STRIDE):
  * 1M-item R2 1.98 s in the triangle form vs 3.9 s dense. */
 int reidmi_rr_rank_rows_f16_ex(const float* feat, int64_t N, int64_t D, int64_t ldf, const float* sqn,
                                const float* nrm, const float* nmax2, const void* feat16, int64_t Np, int64_t Dp,

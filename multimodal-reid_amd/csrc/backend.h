@@ -1,6 +1,9 @@
 // backend.h — the retrieval back end's internal launchers that another source calls, grouped by
-// the file that defines them (internal, not part of the C ABI).  Callers: rerank.hip, search.hip
-// and evalfeat.hip for the row norms, evalfeat.hip for its last stage.
+// the file that defines them (internal, not part of the C ABI).  Callers: the distance launchers
+// from rerank.hip (one-call R1), rerank_rank.hip (R2 chunks) and rerank_jaccard.hip (od chunks),
+// the row norms from search.hip and evalfeat.hip; topk_launch from rerank.hip and rerank_rank.hip;
+// evalfeat.hip its last stage; prefilter.hip's from rerank_rank.hip alone.  The re-rank sources'
+// own cross-file launchers are in rerank.h.
 #pragma once
 #include "common.h"
 

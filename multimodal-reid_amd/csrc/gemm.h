@@ -13,7 +13,7 @@
 //                 dist_rsq the Euclidean distance (rsq_m + csq_n) - 2 acc (distlowp.hip)
 //   EPI_RESID_F16 x fp16 += acc + bias (fp32 sum, one rounding) (out_proj / c_proj + residual, :27-28)
 //   EPI_RRHI      out fp32 = hi(i, j), the upper bound of the exact distance of items i, j from their
-//                 fp16 product (the k-reciprocal re-rank's pre-filter, rerank.hip): only the bound
+//                 fp16 product (the k-reciprocal re-rank's pre-filter, rerank_rank.hip): only the bound
 //                 reaches HBM, and the selection reads 4 bytes per pair instead of 12
 //   EPI_RRSV      no dense output: the pairs of row i that can still matter to its R2 selection
 //                 (hi <= hi_max_i or hi >= lb_i, per-row thresholds from a sampled pass) are

@@ -2,7 +2,7 @@
 // reranking.py:45-48 (od = D / rowmax, stable argsort, first K) selected from bounds of an fp16
 // GEMM and recomputed exactly, in the dense (rank_select1_kernel) and the sampled survivor form
 // (rr_sample_kernel, rank_select_sv_kernel), plus the fp16 feature copy and the norm maxima they
-// need.  Called only from rerank.hip (backend.h); the selection helpers are select.h's.
+// need.  Called only from rerank_rank.hip (backend.h); the selection helpers are select.h's.
 #include "backend.h"
 #include "select.h"
 

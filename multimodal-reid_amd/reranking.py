@@ -4,7 +4,7 @@
         -> np.ndarray float32 (num_query, num_gallery)                  reranking.py:29-100
 
 k-reciprocal encoding + Jaccard re-ranking (Zhong et al., CVPR'17) on the GPU through
-libreidmi (rerank.hip).  Given the same original distances it reproduces the reference's
+libreidmi (rerank*.hip).  Given the same original distances it reproduces the reference's
 numpy arithmetic bit for bit (float32 exp/pairwise sums, float16 V / Jaccard), with ties in
 the initial ranking ordered by index (np.argsort(kind="stable")).  The reference's dense
 N x N float16 V / V_qe become sparse row lists, so MSMT17-size galleries fit.

@@ -1,4 +1,4 @@
-"""GPU parity of k-reciprocal re-ranking (rerank.hip) — bit-exact against the fixtures
+"""GPU parity of k-reciprocal re-ranking (rerank*.hip) — bit-exact against the fixtures
 the reference produced (reranking.py only_local path) and against the oracle."""
 import numpy as np
 import pytest

@@ -23,7 +23,7 @@ from multimodal_reid_amd import synthetic as syn  # noqa: E402
 
 pytestmark = pytest.mark.gpu
 
-JCH = 8192  # gallery columns per Jaccard workgroup (rerank.hip)
+JCH = 8192  # gallery columns per Jaccard workgroup (rerank.h)
 TAIL, IDX_TAIL, DIST_TAIL = 64, -77, np.float32(-12345.5)
 LAM = 0.3
 

@@ -1,5 +1,5 @@
 """First-use costs in a fresh process (profiles/r05/rr_first_call.txt): device allocations of the
-re-rank scratch sizes, the first launch of a rerank.hip kernel, and the staged re-rank before and
+re-rank scratch sizes, the first launch of a libreidmi kernel, and the staged re-rank before and
 after its kernels have run once (small, then MSMT17 size).  python tools/rr_first_call.py"""
 import time, torch, sys, os
 sys.path.insert(0, os.getcwd())
@@ -16,7 +16,7 @@ for gib in (16, 3, 16):
     del b; torch.cuda.empty_cache()
 f = torch.randn(93820, 1280, device=dev)
 s = torch.empty(93820, device=dev)
-t("first rerank.hip launch (row_sqnorm)", lambda: _lib.call("reidmi_row_sqnorm_f32", _lib.ptr(f), 93820, 1280, 1280, _lib.ptr(s), _lib.stream()))
+t("first libreidmi launch (row_sqnorm)", lambda: _lib.call("reidmi_row_sqnorm_f32", _lib.ptr(f), 93820, 1280, 1280, _lib.ptr(s), _lib.stream()))
 t("second launch", lambda: _lib.call("reidmi_row_sqnorm_f32", _lib.ptr(f), 93820, 1280, 1280, _lib.ptr(s), _lib.stream()))
 from multimodal_reid_amd import reranking, evaluate
 q = evaluate.l2_normalize_device(torch.randn(500, 1280, device=dev))
