@@ -51,7 +51,7 @@ int reidmi_gemm_f16_tiled(int epi, const void* A, int64_t lda, const void* W, in
                           int64_t K, const float* bias, const void* rowstat, const float* colsum, void* out,
                           int64_t ldc, int tile, int ngroups, void* stream);
 
-/* One-wave-per-SIMD GEMM prototype (gemm.hip gemm_w4_kernel): out fp16 = A.W^T + bias, same MFMA
+/* One-wave-per-SIMD GEMM prototype (gemm_tools.hip gemm_w4_kernel): out fp16 = A.W^T + bias, same MFMA
  * chain as reidmi_gemm_f16 epi 0 (bit-identical); nostore: the values are computed, not stored.
  * N % 256 == 0, K % 64 == 0, K >= 128. */
 int reidmi_gemm_f16_w4(const void* A, int64_t lda, const void* W, int64_t ldw, int64_t M, int64_t N, int64_t K,

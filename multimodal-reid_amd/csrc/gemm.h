@@ -116,12 +116,25 @@ __device__ __forceinline__ float rr_hi(float dot, float si, float sj, float crn_
 struct GemmOpts {
     int tile = 0;
     int ngroups = 0;
-    int band = -1;  // persistent walk: M-tiles per band (0 = M-major, -1 = auto; gemm.hip tile_mn)
+    int band = -1;  // persistent walk: M-tiles per band (0 = M-major, -1 = auto; gemm_rrsv.h tile_mn)
 };
 
 // Launch C = A . W^T with epilogue `epi`.  Requires N % 128 == 0, K % 64 == 0, lda/ldw
 // multiples of 8 (16-byte rows); M arbitrary.  ea.rowstat / ea.colsum enable the fold.
 int gemm_f16(int epi, const void* A, int64_t lda, const void* W, int64_t ldw, int64_t M, int64_t N, int64_t K,
              const EpiArgs& ea, hipStream_t stream, const GemmOpts& opts = GemmOpts{});
+
+// The body of reidmi_gemm_f16 (reidmi.h) with a tiling choice: checks epi, fills EpiArgs and
+// calls gemm_f16.  Shared with the forced-tiling entry point of gemm_tools.hip.
+int gemm_api(int epi, const void* A, int64_t lda, const void* W, int64_t ldw, int64_t M, int64_t N, int64_t K,
+             const float* bias, const void* rowstat, const float* colsum, void* out, int64_t ldc, const GemmOpts& opt,
+             void* stream);
+
+// Live GEMM timing (gemm_prof.hip, reidmi_prof_*), called by gemm_f16 around its launch.
+// prof_begin returns at once with *end = null while timing is off; otherwise it takes an event
+// pair from the pool, records the start event on s and the record {flops, epi}, and hands back
+// the end event, which prof_end records on s after the launch.
+int prof_begin(double flops, int epi, hipStream_t s, hipEvent_t* end);
+int prof_end(hipEvent_t end, hipStream_t s);
 
 }  // namespace reidmi

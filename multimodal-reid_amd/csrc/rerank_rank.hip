@@ -4,8 +4,8 @@
 //   exact form          distance rows in chunks (distance.hip) -> rowmax_kernel -> top-k (search.hip)
 //   fp16 pre-filter     the fp16 MFMA product bounds every exact distance and only each row's
 //                       candidates are recomputed: dense, sampled and triangle forms, all of them
-//                       drivers of gemm.hip's EPI_RRHI / EPI_RRSV epilogues and prefilter.hip's
-//                       selection kernels; the triangle form also in stages (reidmi_rr_tri_*,
+//                       drivers of the GEMM's EPI_RRHI / EPI_RRSV epilogues (gemm_epilogue.h,
+//                       gemm_rrsv.h) and prefilter.hip's selection kernels; the triangle form also in stages (reidmi_rr_tri_*,
 //                       reidmi_rr_sv_*) for the sharded R2
 //   row utilities       nonzero / gather_rows (the rows the pre-filter leaves for the exact form),
 //                       the transpose of the one-call driver's non-symmetric input
@@ -103,7 +103,7 @@ __global__ void gather_rows_kernel(const float* __restrict__ x, int64_t ldx, int
 // Sampled survivor form of the pre-filter (prefilter.hip rr_sample_kernel / rank_select_sv_kernel):
 // the sample is every S-th item, ns = floor(N / S) rounded down to whole 256-column tiles; per
 // row: the sample's bounds, then the survivor list (RR_SV_CAP pairs) instead of an N-wide row.
-// The selection runs inside the GEMM's epilogue (gemm.hip rrsv_tile): survivors staged in LDS,
+// The selection runs inside the GEMM's epilogue (gemm_rrsv.h rrsv_tile): survivors staged in LDS,
 // row / column records by LDS-DMA, no global memory instruction per tile.  A first version
 // appended straight to the rows' lists (an atomic round trip per row group and tile, its
 // registers spilling the K-loop): 13.0 s at N = 1.01 M against 3.9 + 1.7 s for the dense form
@@ -121,7 +121,7 @@ __global__ void rr_gather_norms_kernel(const float* __restrict__ sqn, const floa
     }
 }
 
-// the survivor epilogue's column records (gemm.hip rrsv_tile) of the rectangular form: (squared
+// the survivor epilogue's column records (gemm_rrsv.h rrsv_tile) of the rectangular form: (squared
 // norm, norm, -, -) of item c, zero past N
 __global__ void rr_colrec_kernel(const float* __restrict__ sqn, const float* __restrict__ nrm, int64_t N, int64_t Np,
                                  float4* __restrict__ out) {

@@ -67,6 +67,51 @@ def test_gemm_epilogues(gpu, epi, M, N, K):
     assert (got - ref).abs().max() <= tol * (ref.abs().max() + 1)
 
 
+def test_gemm_live_timing_records(gpu):
+    """reidmi_prof_*: a record per GEMM while timing is on, filtered by epilogue and by a FLOP
+    floor; every collect clears all records, those it filtered out included; none while off.
+    M = N = 128, K = 64: one workgroup of the small tile."""
+    import ctypes
+    L = _lib()
+    M, N, K = 128, 128, 64
+    A = torch.randn(M, K).half().cuda()
+    W = torch.randn(N, K).half().cuda()
+    bias = torch.randn(N).cuda()
+    out16 = torch.empty(M, N, dtype=torch.float16, device="cuda")
+    out32 = torch.empty(M, N, dtype=torch.float32, device="cuda")
+    ms, cnt, fl = ctypes.c_double(), ctypes.c_int64(), ctypes.c_double()
+    res = (ctypes.byref(ms), ctypes.byref(cnt), ctypes.byref(fl))
+
+    def collected():
+        return cnt.value, fl.value, ms.value
+
+    L.call("reidmi_prof_enable", 1)
+    try:
+        _gemm(L, 0, A, W, bias, out16)
+        _gemm(L, 0, A, W, bias, out16)
+        _gemm(L, 5, A, W, bias, out32)
+        L.call("reidmi_prof_collect_min", 0, 0.0, *res)
+        print("epi 0 of {0, 0, 5}:", collected())
+        assert cnt.value == 2 and fl.value == 2 * 2.0 * M * N * K and ms.value > 0
+        L.call("reidmi_prof_collect", -1, *res)
+        print("all, right after:", collected())
+        assert cnt.value == 0  # the first collect cleared the epi 5 record too
+        _gemm(L, 0, A, W, bias, out16)
+        L.call("reidmi_prof_collect_min", -1, 1e18, *res)
+        print("below the floor:", collected())
+        assert cnt.value == 0
+        L.call("reidmi_prof_collect", -1, *res)
+        print("after the floored collect:", collected())
+        assert cnt.value == 0  # ... and cleared the record it left out
+    finally:
+        L.call("reidmi_prof_enable", 0)
+    _gemm(L, 0, A, W, bias, out16)
+    L.call("reidmi_prof_collect", -1, *res)
+    print("timing off:", collected())
+    assert cnt.value == 0
+    torch.cuda.synchronize()
+
+
 @pytest.mark.parametrize("has_bias", [True, False])
 @pytest.mark.parametrize("epi", [0, 1, 5, 6])
 @pytest.mark.parametrize("M,N,K", [(37, 256, 256), (1, 128, 64)])

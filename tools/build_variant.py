@@ -18,12 +18,16 @@ def main():
     out_dir = os.path.join(ROOT, "tools", "variants")
     os.makedirs(out_dir, exist_ok=True)
     obj = os.path.join(out_dir, f"{name}_{src.replace('.hip', '.o')}")
-    # -DREIDMI_TOOLS: the variant macros are refused without it (gemm.hip / distance.h / prefilter.hip #error)
+    # -DREIDMI_TOOLS: the variant macros are refused without it (gemm_epilogue.h / distance.h / prefilter.hip #error)
     r = subprocess.run([B.HIPCC, *B.FLAGS, B.TOOLS_DEFINE, *defs, "-c", os.path.join(B.CSRC, src), "-o", obj],
                        capture_output=True, text=True)
     if r.returncode:
         sys.exit(r.stderr[-4000:])
-    objs = [obj if f == src else os.path.join(B.OBJ, f.replace(".hip", ".o")) for f in B._sources()]
+    # the other sources: their tools objects where they have one (gemm_tools.hip is tools-only as a
+    # whole, so a gemm.hip variant gets reidmi_gemm_f16_qkv and the rest from there)
+    tools = B._tools_sources()
+    objs = [obj if f == src else os.path.join(B.OBJ, "tools" if f in tools else "", f.replace(".hip", ".o"))
+            for f in B._sources()]
     lib = os.path.join(out_dir, f"libreidmi_{name}.so")
     r = subprocess.run([B.HIPCC, f"--offload-arch={B.ARCH}", "-shared", "-fPIC", "-o", lib, *objs],
                        capture_output=True, text=True)

@@ -1,5 +1,5 @@
 """The QKV GEMM (ln_1 fold + head split, EPI_QKV) across library builds (tools/build_variant.py
-gemm.hip variants, which carry the tools entry reidmi_gemm_f16_qkv), interleaved rounds at a
+gemm.hip variants, linked with gemm_tools.hip's entry reidmi_gemm_f16_qkv), interleaved rounds at a
 batch of B sequences; q / k / v^T outputs checked bit-identical across the builds.
 
     python tools/qkv_lib_ab.py LIB.so,LIB2.so [B] [ROUNDS]"""

@@ -1,5 +1,5 @@
 """Timing variants of the one-wave-per-SIMD GEMM prototype across library builds
-(tools/build_variant.py NAME gemm.hip -DREIDMI_TOOLS -DW4_VAR_...): the mainloop (no stores) of
+(tools/build_variant.py NAME gemm_tools.hip -DW4_VAR_...): the mainloop (no stores) of
 each build on the encoder's shapes, interleaved rounds.
     python tools/w4_var_ab.py LIB.so[,LIB2.so,...] [ROUNDS] [M]"""
 import os
@@ -21,7 +21,7 @@ SHAPES = [("cfc", 3072, 768), ("projp", 768, 3072)]
 def main():
     libs = []
     for p in sys.argv[1].split(","):
-        lib = open_lib(p)  # a variant build: the product entry points plus gemm.hip's tools section
+        lib = open_lib(p)  # a variant build: the product entry points plus the tools sources (gemm_tools.hip)
         w4 = lib.reidmi_gemm_f16_w4
         w4.restype, w4.argtypes = L.declarations(tools=True)["reidmi_gemm_f16_w4"]
         libs.append((os.path.basename(p), lib))
