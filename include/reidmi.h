@@ -32,7 +32,8 @@ const char* reidmi_last_error(void);
  * 6: reidmi_search_merge_f32 added.
  * 7: reidmi_combine_rows_f32 added.
  * 8: reidmi_eval_feat_f32 and the reidmi_evf_* stages added.
- * 9: reidmi_search_bounded_f32 added. */
+ * 9: reidmi_search_bounded_f32 added.
+ * 10: reidmi_dbscan_f32 added. */
 int reidmi_abi_version(void);
 
 /* ------------------------------------------------------------ retrieval back end */
@@ -229,6 +230,33 @@ int reidmi_eval_feat_f32(const float* q, int64_t Q, int64_t ldq, const float* g,
                          const int64_t* g_cams, int cap, int32_t* valid, int64_t* first, int64_t* last,
                          int32_t* npos, double* ap, int64_t* nkept, int32_t* overflow, void* ws, int64_t ws_bytes,
                          void* stream);
+
+/* DBSCAN over the rows of x [N][ldx] fp32 (device, unit column stride, any pitch >= D), from the
+ * features: no N x N matrix is formed, the workspace is linear in N, and the result is the same
+ * on every run.  The distance d(i, j) is reidmi_distmat_f32's of x against itself, bit for bit (the
+ * SQUARED Euclidean distance; its bits are symmetric in i and j), and eps is in those units, the
+ * scale of reidmi_search_bounded_f32's radius.
+ *   neighbours  j is a neighbour of i iff d(i, j) <= eps or j == i (the diagonal counts whatever
+ *               its rounding gave); counts[i] = the number of neighbours of i, itself included
+ *   core        core[i] = 1 iff counts[i] >= min_samples, else 0
+ *   clusters    the connected components of the core points under the neighbour relation, numbered
+ *               0, 1, ... in ascending order of each component's lowest core index
+ *   border      a non-core point with a core neighbour takes the smallest cluster number among its
+ *               core neighbours' clusters
+ *   noise       everything else: labels[i] = -1
+ * which is what scikit-learn's DBSCAN (metric="precomputed", on the same distances) labels.
+ * Outputs (device): labels int32 [N], counts int32 [N], core uint8 [N], n_clusters one int32.
+ * Three passes over the 128 x 128 distance tiles (count, union of the core pairs, border), each the
+ * N x N x D work of reidmi_distmat_f32 without its stores; the union and border passes skip the
+ * tiles without a core column.  ws: reidmi_dbscan_workspace_bytes(N, D) bytes, 16-byte aligned:
+ * the squared norms and three int32 arrays of N entries plus N / 2048 block sums (negative on bad
+ * arguments).  Refused with REIDMI_EINVAL before any HIP call: a null pointer, N < 1, N >= 2^31,
+ * D < 1, ldx < D, eps negative or not finite, min_samples < 1, a short or misaligned workspace.
+ * No allocation or synchronisation inside. */
+int64_t reidmi_dbscan_workspace_bytes(int64_t N, int64_t D);
+int reidmi_dbscan_f32(const float* x, int64_t N, int64_t D, int64_t ldx, float eps, int min_samples,
+                      int32_t* labels, int32_t* counts, uint8_t* core, int32_t* n_clusters, void* ws,
+                      int64_t ws_bytes, void* stream);
 
 
 /* k-reciprocal re-ranking — re_ranking(probFea, galFea, k1, k2, lambda_value) (reranking.py:29-100),

@@ -19,5 +19,6 @@ REIDMI_API const char* reidmi_last_error(void) { return reidmi::g_err.c_str(); }
 // 6: merged rank lists (reidmi_search_merge_f32);
 // 7: combined feature rows (reidmi_combine_rows_f32);
 // 8: matrix-free evaluation (reidmi_eval_feat_f32, reidmi_evf_*);
-// 9: bounded search (reidmi_search_bounded_f32).
-REIDMI_API int reidmi_abi_version(void) { return 9; }
+// 9: bounded search (reidmi_search_bounded_f32);
+// 10: clustering (reidmi_dbscan_f32).
+REIDMI_API int reidmi_abi_version(void) { return 10; }
