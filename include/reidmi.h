@@ -33,7 +33,8 @@ const char* reidmi_last_error(void);
  * 7: reidmi_combine_rows_f32 added.
  * 8: reidmi_eval_feat_f32 and the reidmi_evf_* stages added.
  * 9: reidmi_search_bounded_f32 added.
- * 10: reidmi_dbscan_f32 added. */
+ * 10: reidmi_dbscan_f32 added.
+ * 11: reidmi_rr_jaccard_self_rows and reidmi_dbscan_jaccard added. */
 int reidmi_abi_version(void);
 
 /* ------------------------------------------------------------ retrieval back end */
@@ -430,6 +431,46 @@ int reidmi_rr_jaccard_topk_rows(const float* feat, int64_t N, int64_t D, int64_t
                                 const int64_t* g_cams, int32_t* out_idx, float* out_dist, int64_t ldo, float* chunk,
                                 int64_t chunk_rows, void* bounds, int64_t bounds_bytes, void* ws, int64_t ws_bytes,
                                 void* stream);
+/* The Jaccard term alone, of the N items against themselves (reranking.py:86-93 for every row i in
+ * [0, N) over every column j in [0, N); the number of queries plays no part in V_qe):
+ *   tm(i, j) = the sequential fp16 sum, over the nonzero columns c of V_qe[i] in ascending c, of
+ *              min(V_qe[i, c], V_qe[j, c])
+ *   jd(i, j) = 1 - tm / (2 - tm), every operation rounded to fp16
+ * which is the Jaccard half of reidmi_rr_jaccard_rows' blend, from the same walk: the same bits.
+ * The bits are symmetric in i and j; a diagonal entry is small but need not be zero, an entry may
+ * be slightly negative (tm rounds above 1), and jd(i, j) = 1 exactly where V_qe[i] and V_qe[j]
+ * share no column.  This is the Jaccard distance of the reference's re_ranking; other code bases'
+ * compute_jaccard_distance variants build V differently and give other values.
+ * out [hi-lo][ldo] uint16 (fp16 bits, ldo >= N): rows lo..hi over all N columns, the dense form for
+ * small N.  qoff / qcol / qval: V_qe of all N rows (CSR); coff / irow / ival: its inverted index
+ * (reidmi_rr_csc); bounds: reidmi_rr_jaccard_bounds_bytes(N, N) bytes, 8-byte aligned.  Refused
+ * with REIDMI_EINVAL before any HIP call: a null pointer, N < 1, N >= 2^31, a row range outside
+ * 0 <= lo <= hi <= N, ldo < N, short or misaligned bounds. */
+int reidmi_rr_jaccard_self_rows(int64_t N, int64_t lo, int64_t hi, const int64_t* qoff, const int32_t* qcol,
+                                const uint16_t* qval, const int64_t* coff, const int32_t* irow,
+                                const uint16_t* ival, uint16_t* out, int64_t ldo, void* bounds, int64_t bounds_bytes,
+                                void* stream);
+/* DBSCAN of the N items on that distance, from the sparse rows: no N x N matrix is formed and the
+ * result is the same on every run.  The rules and the outputs are reidmi_dbscan_f32's with d
+ * replaced by jd: eps is rounded to fp16 (to nearest even) and compared with the fp16 jd, j is a
+ * neighbour of i iff jd(i, j) <= eps16 or j == i; counts, core, clusters numbered by lowest core
+ * index, border points to the smallest cluster number, noise = -1 as there.  The rounded eps must
+ * satisfy 0 <= eps16 < 1: a pair without a shared column has jd = 1 and is never visited, which
+ * is what makes the three passes (count, union of the core pairs, border) sparse.  Each pass runs
+ * one workgroup per (row, 8192-column chunk) that returns at once when no inverted list of the
+ * row's columns has an entry in the chunk.
+ * Inputs: V_qe of all N rows and its inverted index, as for reidmi_rr_jaccard_self_rows.
+ * ws: reidmi_dbscan_jaccard_workspace_bytes(N) bytes, 16-byte aligned: three int32 arrays of N
+ * entries, N / 2048 block sums, and the chunk bounds of the inverted lists, N * (ceil(N / 8192) + 1)
+ * * 8 bytes (11 MB at 100 000 rows, about 1 GB at 1M; negative on bad arguments).  Refused with
+ * REIDMI_EINVAL before any HIP call: a null pointer, N < 1, N >= 2^31, eps negative, not finite or
+ * rounding to >= 1 in fp16, min_samples < 1, a short or misaligned workspace.  No allocation or
+ * synchronisation inside. */
+int64_t reidmi_dbscan_jaccard_workspace_bytes(int64_t N);
+int reidmi_dbscan_jaccard(int64_t N, const int64_t* qoff, const int32_t* qcol, const uint16_t* qval,
+                          const int64_t* coff, const int32_t* irow, const uint16_t* ival, float eps, int min_samples,
+                          int32_t* labels, int32_t* counts, uint8_t* core, int32_t* n_clusters, void* ws,
+                          int64_t ws_bytes, void* stream);
 /* Row utilities of the staged driver's exact-row fallback (reranking.HipStages): row maxima
  * skipping NaN (the od divisors, reranking.py:46); ordered compaction idx[0..*count) = positions
  * of the nonzero flags (np.nonzero; count: device int32); out[r] = x[row0 + idx[r]] (fp32 rows). */

@@ -20,5 +20,7 @@ REIDMI_API const char* reidmi_last_error(void) { return reidmi::g_err.c_str(); }
 // 7: combined feature rows (reidmi_combine_rows_f32);
 // 8: matrix-free evaluation (reidmi_eval_feat_f32, reidmi_evf_*);
 // 9: bounded search (reidmi_search_bounded_f32);
-// 10: clustering (reidmi_dbscan_f32).
-REIDMI_API int reidmi_abi_version(void) { return 10; }
+// 10: clustering (reidmi_dbscan_f32);
+// 11: clustering on the k-reciprocal Jaccard distance (reidmi_rr_jaccard_self_rows,
+//     reidmi_dbscan_jaccard).
+REIDMI_API int reidmi_abi_version(void) { return 11; }

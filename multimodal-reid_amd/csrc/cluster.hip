@@ -4,7 +4,7 @@
 // Three passes over the distance tiles of x against itself, each the mainloop of the distance
 // kernels (distance.h), so d(i, j) has reidmi_distmat_f32's bits, and none stores a tile:
 //   count    hits per row (d <= eps, or the diagonal) -> counts; then core = counts >= min_samples
-//   union    every core pair within eps joins its two trees in parent[] (lock-free, below)
+//   union    every core pair within eps joins its two trees in parent[] (lock-free, cluster.h)
 //   border   every non-core row takes the smallest root among its core columns within eps
 // and between / after them the O(N) kernels: init, compress (every parent becomes its root), the
 // scan of the root flags into cluster numbers, and the labels.
@@ -18,6 +18,7 @@
 // returns the entry's value, and the walk goes on from there.  Every retry follows a strictly
 // smaller index, nobody waits for anybody.  Counts are integer sums, border roots integer minima.
 #include "backend.h"
+#include "cluster.h"
 #include "distance.h"
 
 namespace reidmi {
@@ -25,34 +26,6 @@ namespace reidmi {
 constexpr int DBS_SLOTS = 1024;                      // 256 CUs x DM2_MINWG
 constexpr int DBS_SMEM = 2 * 2 * DM2_BK * DM2_LD;    // floats: both mainloops' stages
 static_assert(DBS_SMEM >= 2 * DM_BK * (DM_BM + DM_PAD), "dbs_tile: both mainloops' stages fit");
-constexpr int DBS_NONE = 0x7fffffff;                 // border root of a row without a core neighbour
-enum DbsPass : int { DBS_COUNT = 0, DBS_UNION = 1, DBS_BORDER = 2 };
-
-__device__ __forceinline__ int dbs_load(const int32_t* p) {
-    return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
-}
-
-__device__ __forceinline__ int dbs_find(const int32_t* parent, int a) {
-    for (;;) {
-        const int p = dbs_load(parent + a);  // p <= a: the walk ends
-        if (p == a) return a;
-        a = p;
-    }
-}
-
-// Joins the trees of a and b; returns the joined tree's root as far as this thread saw it.
-__device__ __forceinline__ int dbs_union(int32_t* parent, int a, int b) {
-    for (;;) {
-        a = dbs_find(parent, a);
-        b = dbs_find(parent, b);
-        if (a == b) return a;
-        const int hi = a > b ? a : b, lo = a > b ? b : a;
-        const int old = atomicCAS(&parent[hi], hi, lo);
-        if (old == hi) return lo;
-        a = old;  // hi was hooked meanwhile, under old < hi
-        b = lo;
-    }
-}
 
 // evf_count_kernel's structure: a workgroup owns one 128-row band and one contiguous column range
 // [c0, c1) and walks it in 128-column tiles.  Row state in LDS.  LDS: 33 024 B of operand stages
@@ -287,19 +260,51 @@ __global__ __launch_bounds__(256) void dbs_labels_kernel(const uint8_t* __restri
 }
 
 // ------------------------------------------------------------------------- launchers
-// workspace: norms | parent | border | number | block sums
-struct DbsWs {
-    int64_t parent_off, border_off, number_off, bsum_off, nb, bytes;
-};
-static bool dbs_ws(int64_t N, int64_t D, DbsWs* w) {
-    if (N < 1 || N >= (1ll << 31) || D < 1) return false;
+bool dbs_state(int64_t N, DbsState* w) {
+    if (N < 1 || N >= (1ll << 31)) return false;
     const int64_t row = (N * 4 + 15) / 16 * 16;
     w->nb = (N + DBS_SCAN - 1) / DBS_SCAN;
-    w->parent_off = row;
-    w->border_off = 2 * row;
-    w->number_off = 3 * row;
-    w->bsum_off = 4 * row;
-    w->bytes = 4 * row + (w->nb * 4 + 15) / 16 * 16;
+    w->parent_off = 0;
+    w->border_off = row;
+    w->number_off = 2 * row;
+    w->bsum_off = 3 * row;
+    w->bytes = 3 * row + (w->nb * 4 + 15) / 16 * 16;
+    return true;
+}
+
+int dbs_init_launch(const int32_t* counts, int64_t N, int min_samples, uint8_t* core, int32_t* parent, int32_t* border,
+                    hipStream_t s) {
+    hipLaunchKernelGGL(dbs_init_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, counts, N, min_samples,
+                       core, parent, border);
+    RM_LAUNCHED();
+    return OK;
+}
+
+int dbs_compress_launch(int32_t* parent, int64_t N, hipStream_t s) {
+    hipLaunchKernelGGL(dbs_compress_kernel, dim3((unsigned)((N + 255) / 256)), dim3(256), 0, s, parent, N);
+    RM_LAUNCHED();
+    return OK;
+}
+
+int dbs_labels_launch(const uint8_t* core, const int32_t* parent, const int32_t* border, int32_t* number, int32_t* bsum,
+                      int64_t nb, int64_t N, int32_t* n_clusters, int32_t* labels, hipStream_t s) {
+    const dim3 rows((unsigned)((N + 255) / 256)), blocks((unsigned)nb);
+    hipLaunchKernelGGL(dbs_scan_sums_kernel, blocks, dim3(256), 0, s, core, parent, N, bsum);
+    RM_LAUNCHED();
+    hipLaunchKernelGGL(dbs_scan_offsets_kernel, dim3(1), dim3(256), 0, s, bsum, nb, n_clusters);
+    RM_LAUNCHED();
+    hipLaunchKernelGGL(dbs_scan_number_kernel, blocks, dim3(256), 0, s, core, parent, N, (const int32_t*)bsum, number);
+    RM_LAUNCHED();
+    hipLaunchKernelGGL(dbs_labels_kernel, rows, dim3(256), 0, s, core, parent, border, (const int32_t*)number, N,
+                       labels);
+    RM_LAUNCHED();
+    return OK;
+}
+
+// workspace: norms | the O(N) state (cluster.h)
+static bool dbs_ws(int64_t N, int64_t D, DbsState* w, int64_t* bytes) {
+    if (D < 1 || !dbs_state(N, w)) return false;
+    *bytes = (N * 4 + 15) / 16 * 16 + w->bytes;
     return true;
 }
 
@@ -335,8 +340,9 @@ using namespace reidmi;
     } while (0)
 
 REIDMI_API int64_t reidmi_dbscan_workspace_bytes(int64_t N, int64_t D) {
-    DbsWs w;
-    return dbs_ws(N, D, &w) ? w.bytes : -1;
+    DbsState w;
+    int64_t bytes;
+    return dbs_ws(N, D, &w, &bytes) ? bytes : -1;
 }
 
 REIDMI_API int reidmi_dbscan_f32(const float* x, int64_t N, int64_t D, int64_t ldx, float eps, int min_samples,
@@ -349,37 +355,24 @@ REIDMI_API int reidmi_dbscan_f32(const float* x, int64_t N, int64_t D, int64_t l
     RM_REQUIRE(x != nullptr, "dbscan: features required");
     RM_REQUIRE(labels != nullptr && counts != nullptr && core != nullptr && n_clusters != nullptr,
                "dbscan: labels, counts, core and n_clusters required");
-    DbsWs w;
-    RM_REQUIRE(dbs_ws(N, D, &w) && ws != nullptr && ((uintptr_t)ws & 15) == 0 && ws_bytes >= w.bytes,
+    DbsState w;
+    int64_t bytes;
+    RM_REQUIRE(dbs_ws(N, D, &w, &bytes) && ws != nullptr && ((uintptr_t)ws & 15) == 0 && ws_bytes >= bytes,
                "dbscan: workspace (reidmi_dbscan_workspace_bytes, 16-byte aligned) required");
     hipStream_t s = (hipStream_t)stream;
     float* xx = (float*)ws;
-    int32_t* parent = (int32_t*)((char*)ws + w.parent_off);
-    int32_t* border = (int32_t*)((char*)ws + w.border_off);
-    int32_t* number = (int32_t*)((char*)ws + w.number_off);
-    int32_t* bsum = (int32_t*)((char*)ws + w.bsum_off);
-    const dim3 rows((unsigned)((N + 255) / 256)), blocks((unsigned)w.nb);
+    char* state = (char*)ws + (bytes - w.bytes);
+    int32_t* parent = (int32_t*)(state + w.parent_off);
+    int32_t* border = (int32_t*)(state + w.border_off);
+    int32_t* number = (int32_t*)(state + w.number_off);
+    int32_t* bsum = (int32_t*)(state + w.bsum_off);
     RM_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)N * 4, s));
     rows_sqnorm_launch(x, N, D, ldx, xx, s);
     RM_LAUNCHED();
     DBS_TRY(dbs_pass_run<DBS_COUNT>(x, xx, N, D, ldx, eps, core, counts, parent, border, s));
-    hipLaunchKernelGGL(dbs_init_kernel, rows, dim3(256), 0, s, (const int32_t*)counts, N, min_samples, core, parent,
-                       border);
-    RM_LAUNCHED();
+    DBS_TRY(dbs_init_launch(counts, N, min_samples, core, parent, border, s));
     DBS_TRY(dbs_pass_run<DBS_UNION>(x, xx, N, D, ldx, eps, core, counts, parent, border, s));
-    hipLaunchKernelGGL(dbs_compress_kernel, rows, dim3(256), 0, s, parent, N);
-    RM_LAUNCHED();
+    DBS_TRY(dbs_compress_launch(parent, N, s));
     DBS_TRY(dbs_pass_run<DBS_BORDER>(x, xx, N, D, ldx, eps, core, counts, parent, border, s));
-    hipLaunchKernelGGL(dbs_scan_sums_kernel, blocks, dim3(256), 0, s, (const uint8_t*)core, (const int32_t*)parent, N,
-                       bsum);
-    RM_LAUNCHED();
-    hipLaunchKernelGGL(dbs_scan_offsets_kernel, dim3(1), dim3(256), 0, s, bsum, w.nb, n_clusters);
-    RM_LAUNCHED();
-    hipLaunchKernelGGL(dbs_scan_number_kernel, blocks, dim3(256), 0, s, (const uint8_t*)core, (const int32_t*)parent,
-                       N, (const int32_t*)bsum, number);
-    RM_LAUNCHED();
-    hipLaunchKernelGGL(dbs_labels_kernel, rows, dim3(256), 0, s, (const uint8_t*)core, (const int32_t*)parent,
-                       (const int32_t*)border, (const int32_t*)number, N, labels);
-    RM_LAUNCHED();
-    return OK;
+    return dbs_labels_launch(core, parent, border, number, bsum, w.nb, N, n_clusters, labels, s);
 }

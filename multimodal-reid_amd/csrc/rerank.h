@@ -2,7 +2,8 @@
 // the C ABI; the stage map is at the head of rerank.hip).  The sources and their boundaries:
 //   rerank_rank.hip     R2: rank rows (exact and with the fp16 pre-filter), small row utilities
 //   rerank_rows.hip     R3-R5: V rows, query expansion, ELL -> CSR, the inverted index
-//   rerank_jaccard.hip  R6+R7: the Jaccard blend, as a matrix or as rank lists
+//   rerank_jaccard.hip  R6+R7: the Jaccard blend, as a matrix or as rank lists; the Jaccard term
+//                       alone of the set against itself, as rows or as DBSCAN's passes (cluster.h)
 //   rerank.hip          the one-call driver over all of them
 // Here: the capacity constants and the plans derived from them, the sparse row views and the
 // distance source that pass from stage to stage, and the host launchers one source calls in

@@ -7,9 +7,14 @@
 //     + jaccard_merge_kernel  one merge per query (reidmi_rr_jaccard_topk_rows)
 //   jaccard_scan_kernel     the matrix form over unsorted lists (the one-call driver, through
 //                           jaccard_scan_launch of rerank.h)
-// Boundary: from V_qe and its inverted index to final distances or rank lists.  JCH (rerank.h) is
-// read only here: the kernels' chunk and every grid and byte count derived from it.
+//   jaccard_self_kernel     the Jaccard term alone of the N items against themselves, as fp16 rows
+//                           (reidmi_rr_jaccard_self_rows) or as the count / union / border passes
+//                           of DBSCAN on it (reidmi_dbscan_jaccard; the O(N) kernels: cluster.h)
+// Boundary: from V_qe and its inverted index to final distances, rank lists or cluster labels.  JCH
+// (rerank.h) is read only here: the kernels' chunk and every grid and byte count derived from it,
+// which is why the DBSCAN passes over the chunks live here and not in cluster.hip.
 #include "backend.h"
+#include "cluster.h"
 #include "rerank.h"
 #include "select.h"
 
@@ -46,13 +51,17 @@ __global__ __launch_bounds__(256) void jaccard_bounds_kernel(const int64_t* __re
 
 // One final distance: tm = temp_min's fp16 bits, od the unscaled original distance, dv the query's
 // od divisor, lam = fp32 of the fp16 (1 - lambda).  Jaccard in fp16 (every op rounded,
-// reranking.py:93), the blend in fp32 (reranking.py:95).  The one definition for every Jaccard
-// kernel, matrix or selecting form.
-__device__ __forceinline__ float jaccard_blend_one(uint16_t tm, float od, float dv, float lam, float lam_f) {
+// reranking.py:93: jaccard_jac_bits, the distance the self form stops at), the blend in fp32
+// (reranking.py:95).  The one definition for every Jaccard kernel, matrix, selecting or self form.
+__device__ __forceinline__ uint16_t jaccard_jac_bits(uint16_t tm) {
     const float tv = h2f_bits(tm);
     const uint16_t den = f2h_bits(2.0f - tv);
     const uint16_t qt = f2h_bits(tv / h2f_bits(den));
-    const uint16_t jac = f2h_bits(1.0f - h2f_bits(qt));
+    return f2h_bits(1.0f - h2f_bits(qt));
+}
+
+__device__ __forceinline__ float jaccard_blend_one(uint16_t tm, float od, float dv, float lam, float lam_f) {
+    const uint16_t jac = jaccard_jac_bits(tm);
     const float a = h2f_bits(f2h_bits(h2f_bits(jac) * lam));
     const float b = (od / dv) * lam_f;
     return a + b;
@@ -64,6 +73,64 @@ __device__ __forceinline__ void jaccard_blend(const uint16_t* tmin, int span, co
                                               uint16_t lam16, float lam_f, float* __restrict__ out) {
     const float lam = h2f_bits(lam16);
     for (int t = threadIdx.x; t < span; t += blockDim.x) out[t] = jaccard_blend_one(tmin[t], od[t], dv, lam, lam_f);
+}
+
+// The walk of one (row i, chunk) over sorted lists, for every kernel that has tmin (fp16 bits, JCH
+// entries in LDS, zeroed, a barrier passed): on return, behind its last barrier, tmin[r - base] is
+// temp_min of chunk column r.  cbnd: the bounds of jaccard_bounds_kernel, nb1 = chunks + 1 per
+// column; base: the first row index of the chunk.
+__device__ __forceinline__ void jaccard_walk(uint16_t* tmin, const Rows& Vq, int64_t i, int64_t base,
+                                             const int32_t* __restrict__ irow, const uint16_t* __restrict__ ival,
+                                             const int64_t* __restrict__ cbnd, int64_t chunk, int nb1) {
+    const int nz = Vq.len(i);
+    const int64_t qb = Vq.beg(i);
+    // V_qe[i]'s columns in batches of 256: each thread fetches one column's value and slice
+    // bounds (jaccard_bounds_kernel) at once, so the column walk below has no dependent
+    // bound loads; a thread's element of the next column's slice is loaded before the
+    // barrier of the current one
+    __shared__ int64_t s_p0[256];
+    __shared__ int s_n[256];
+    __shared__ float s_vi[256];
+    for (int e0 = 0; e0 < nz; e0 += 256) {
+        const int m = nz - e0 < 256 ? nz - e0 : 256;
+        if ((int)threadIdx.x < m) {
+            const int32_t c = Vq.col[qb + e0 + threadIdx.x];
+            const int64_t p0 = cbnd[(int64_t)c * nb1 + chunk], p1 = cbnd[(int64_t)c * nb1 + chunk + 1];
+            s_p0[threadIdx.x] = p0;
+            s_n[threadIdx.x] = (int)(p1 - p0);
+            s_vi[threadIdx.x] = h2f_bits(Vq.val[qb + e0 + threadIdx.x]);
+        }
+        __syncthreads();
+        int nk = -1;
+        float nv = 0.0f;
+        auto fetch = [&](int e) {
+            nk = -1;
+            if ((int)threadIdx.x < s_n[e]) {
+                const int64_t p = s_p0[e] + threadIdx.x;
+                nk = (int)(irow[p] - base);
+                nv = h2f_bits(ival[p]);
+            }
+        };
+        fetch(0);
+        for (int e = 0; e < m; e++) {
+            const int k = nk;
+            const float vr = nv;
+            const float vi = s_vi[e];
+            const int n = s_n[e];
+            if (e + 1 < m) fetch(e + 1);
+            if (k >= 0) {
+                const float mn = vr < vi ? vr : vi;
+                tmin[k] = f2h_bits(h2f_bits(tmin[k]) + mn);
+            }
+            for (int64_t p = s_p0[e] + 256 + threadIdx.x; p < s_p0[e] + n; p += blockDim.x) {  // long slices
+                const int kk = (int)(irow[p] - base);
+                const float vr2 = h2f_bits(ival[p]);
+                const float mn = vr2 < vi ? vr2 : vi;
+                tmin[kk] = f2h_bits(h2f_bits(tmin[kk]) + mn);
+            }
+            __syncthreads();
+        }
+    }
 }
 
 // jaccard_kernel<false> is the matrix form above.  jaccard_kernel<true> is the selecting form
@@ -102,56 +169,7 @@ __global__ __launch_bounds__(256) void jaccard_kernel(const float* __restrict__ 
     const int span = (int)(end - base);
     for (int t = threadIdx.x; t < span; t += blockDim.x) tmin[t] = 0;
     __syncthreads();
-    const int nz = Vq.len(i);
-    const int64_t qb = Vq.beg(i);
-    const int nb1 = (int)gridDim.x + 1;
-    // V_qe[i]'s columns in batches of 256: each thread fetches one column's value and slice
-    // bounds (jaccard_bounds_kernel) at once, so the column walk below has no dependent
-    // bound loads; a thread's element of the next column's slice is loaded before the
-    // barrier of the current one
-    __shared__ int64_t s_p0[256];
-    __shared__ int s_n[256];
-    __shared__ float s_vi[256];
-    for (int e0 = 0; e0 < nz; e0 += 256) {
-        const int m = nz - e0 < 256 ? nz - e0 : 256;
-        if ((int)threadIdx.x < m) {
-            const int32_t c = Vq.col[qb + e0 + threadIdx.x];
-            const int64_t p0 = cbnd[(int64_t)c * nb1 + blockIdx.x], p1 = cbnd[(int64_t)c * nb1 + blockIdx.x + 1];
-            s_p0[threadIdx.x] = p0;
-            s_n[threadIdx.x] = (int)(p1 - p0);
-            s_vi[threadIdx.x] = h2f_bits(Vq.val[qb + e0 + threadIdx.x]);
-        }
-        __syncthreads();
-        int nk = -1;
-        float nv = 0.0f;
-        auto fetch = [&](int e) {
-            nk = -1;
-            if ((int)threadIdx.x < s_n[e]) {
-                const int64_t p = s_p0[e] + threadIdx.x;
-                nk = (int)(irow[p] - base);
-                nv = h2f_bits(ival[p]);
-            }
-        };
-        fetch(0);
-        for (int e = 0; e < m; e++) {
-            const int k = nk;
-            const float vr = nv;
-            const float vi = s_vi[e];
-            const int n = s_n[e];
-            if (e + 1 < m) fetch(e + 1);
-            if (k >= 0) {
-                const float mn = vr < vi ? vr : vi;
-                tmin[k] = f2h_bits(h2f_bits(tmin[k]) + mn);
-            }
-            for (int64_t p = s_p0[e] + 256 + threadIdx.x; p < s_p0[e] + n; p += blockDim.x) {  // long slices
-                const int kk = (int)(irow[p] - base);
-                const float vr2 = h2f_bits(ival[p]);
-                const float mn = vr2 < vi ? vr2 : vi;
-                tmin[kk] = f2h_bits(h2f_bits(tmin[kk]) + mn);
-            }
-            __syncthreads();
-        }
-    }
+    jaccard_walk(tmin, Vq, i, base, irow, ival, cbnd, blockIdx.x, (int)gridDim.x + 1);
     if constexpr (!SELECT) {
         jaccard_blend(tmin, span, OD + y * ld + (base - odc0), rowdiv[i], lam16, lam_f, out + y * ldo + (base - Q));
     } else {
@@ -184,6 +202,96 @@ __global__ __launch_bounds__(256) void jaccard_merge_kernel(const float2* __rest
     const float2* __restrict__ mine = part + y * chunks * (int64_t)K;
     topk_merge_dev([&](int64_t p) { return mine[p]; }, (int64_t)chunks * K, K, L, out_idx + y * ldo,
                    out_dist ? out_dist + y * ldo : nullptr);
+}
+
+// ----------------------------------------------------------- the self form
+// jd(i, j) = the Jaccard term alone (reranking.py:86-93, jaccard_jac_bits) of every row i against
+// every column j of the same N items: Q = 0 in the bounds, the same walk, so temp_min has the
+// matrix form's bits.  One workgroup per (row, chunk), the chunks of a row adjacent in the grid.
+//   JS_ROWS      the fp16 bits of the chunk's jd -> out (the dense form: small N, tests)
+//   DBS_COUNT    hits of row i in the chunk (jd <= eps, or the diagonal): one atomic add
+//   DBS_UNION    core rows only: every core hit j > i joins i's tree (cluster.h)
+//   DBS_BORDER   non-core rows only: the smallest final parent[] among the core hits, one atomicMin
+// jd < 1 only where V_qe[i] and V_qe[j] share a column, that is, where a list of one of V_qe[i]'s
+// columns has an entry in the chunk: a workgroup that finds all its slices empty returns before it
+// zeroes tmin (JS_ROWS: after writing jd = 1), and eps < 1 makes that exact.  The chunk that holds
+// i itself is never skipped (the diagonal counts whatever V_qe[i] holds).  UNION and BORDER return
+// at once for rows that are not of their kind.
+constexpr int JS_ROWS = 3;  // beside DbsPass
+
+template <int PASS>
+__global__ __launch_bounds__(256) void jaccard_self_kernel(int64_t N, int64_t row0, int nch, Rows Vq,
+                                                           const int32_t* __restrict__ irow,
+                                                           const uint16_t* __restrict__ ival,
+                                                           const int64_t* __restrict__ cbnd, float eps,
+                                                           const uint8_t* __restrict__ core,
+                                                           int32_t* __restrict__ counts, int32_t* parent,
+                                                           int32_t* __restrict__ border, uint16_t* __restrict__ out,
+                                                           int64_t ldo) {
+    __shared__ uint16_t tmin[JCH];
+    __shared__ int s_acc;  // COUNT: the chunk's hits; BORDER: its smallest root
+    const int64_t y = blockIdx.x / (unsigned)nch;
+    const int64_t chunk = blockIdx.x - y * nch;
+    const int64_t i = row0 + y;
+    if constexpr (PASS == DBS_UNION || PASS == DBS_BORDER) {
+        if ((core[i] != 0) != (PASS == DBS_UNION)) return;
+    }
+    const int64_t base = chunk * JCH;
+    const int64_t end = base + JCH < N ? base + JCH : N;
+    const int span = (int)(end - base);
+    const int nz = Vq.len(i);
+    const int64_t qb = Vq.beg(i);
+    bool any = base <= i && i < end;
+    for (int e = threadIdx.x; e < nz && !any; e += blockDim.x) {
+        const int64_t b = (int64_t)Vq.col[qb + e] * (nch + 1) + chunk;
+        any = cbnd[b + 1] > cbnd[b];
+    }
+    if (!__syncthreads_or(any)) {
+        if constexpr (PASS == JS_ROWS) {
+            const uint16_t one = jaccard_jac_bits(0);
+            for (int t = threadIdx.x; t < span; t += blockDim.x) out[y * ldo + base + t] = one;
+        }
+        return;
+    }
+    for (int t = threadIdx.x; t < span; t += blockDim.x) tmin[t] = 0;
+    if (threadIdx.x == 0) s_acc = PASS == DBS_BORDER ? DBS_NONE : 0;
+    __syncthreads();
+    jaccard_walk(tmin, Vq, i, base, irow, ival, cbnd, chunk, nch + 1);
+    if constexpr (PASS == JS_ROWS) {
+        for (int t = threadIdx.x; t < span; t += blockDim.x) out[y * ldo + base + t] = jaccard_jac_bits(tmin[t]);
+    } else {
+        int acc = PASS == DBS_BORDER ? DBS_NONE : 0;
+        for (int t = threadIdx.x; t < span; t += blockDim.x) {
+            const int64_t j = base + t;
+            const bool hit = h2f_bits(jaccard_jac_bits(tmin[t])) <= eps;
+            if constexpr (PASS == DBS_COUNT) {
+                acc += hit || j == i;
+            } else if constexpr (PASS == DBS_UNION) {
+                if (hit && i < j && core[j] != 0) dbs_union(parent, (int)i, (int)j);
+            } else {
+                if (hit && core[j] != 0) {
+                    const int r = parent[j];  // final roots
+                    acc = r < acc ? r : acc;
+                }
+            }
+        }
+        if constexpr (PASS == DBS_COUNT) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o, 64);
+            if ((threadIdx.x & 63) == 0 && acc != 0) atomicAdd(&s_acc, acc);
+            __syncthreads();
+            if (threadIdx.x == 0 && s_acc != 0) atomicAdd(&counts[i], s_acc);
+        } else if constexpr (PASS == DBS_BORDER) {
+#pragma unroll
+            for (int o = 32; o > 0; o >>= 1) {
+                const int u = __shfl_xor(acc, o, 64);
+                acc = u < acc ? u : acc;
+            }
+            if ((threadIdx.x & 63) == 0 && acc != DBS_NONE) atomicMin(&s_acc, acc);
+            __syncthreads();
+            if (threadIdx.x == 0 && s_acc != DBS_NONE) atomicMin(&border[i], s_acc);
+        }
+    }
 }
 
 // Jaccard over unsorted inverted lists: every chunk scans whole lists and filters rows.
@@ -245,6 +353,46 @@ constexpr int JT_K_MAX = 128;
 static int64_t jaccard_topk_ws_bytes(int64_t rows, int64_t G, int k) {
     if (rows < 1 || rows > 65535 || G < 1 || G >= 0x7fffffff || k < 1 || k > JT_K_MAX || k > G) return -1;
     return rows * ((G + JCH - 1) / JCH) * k * 8;
+}
+
+// The self form's launches.  A launch holds fewer than 2^31 threads: the bounds go column slab by
+// column slab (a slab's lists are addressed through the same irow, its bounds behind the previous
+// slab's), a pass row slab by row slab.
+constexpr int64_t JS_THREADS = 1ll << 31;
+
+static int jaccard_self_bounds(int64_t N, const int64_t* coff, const int32_t* irow, int64_t* cbnd, hipStream_t s) {
+    const int nch = ceil_div(N, JCH);
+    const int64_t per = JS_THREADS / (nch + 1);
+    for (int64_t c0 = 0; c0 < N; c0 += per) {
+        const int64_t n = N - c0 < per ? N - c0 : per;
+        hipLaunchKernelGGL(jaccard_bounds_kernel, dim3(ceil_div(n * (nch + 1), 256)), dim3(256), 0, s, coff + c0, irow,
+                           n, (int64_t)0, nch, cbnd + c0 * (nch + 1));
+        RM_LAUNCHED();
+    }
+    return OK;
+}
+
+template <int PASS>
+static int jaccard_self_run(int64_t N, int64_t lo, int64_t hi, const Rows& Vq, const int32_t* irow,
+                            const uint16_t* ival, const int64_t* cbnd, float eps, const uint8_t* core,
+                            int32_t* counts, int32_t* parent, int32_t* border, uint16_t* out, int64_t ldo,
+                            hipStream_t s) {
+    const int nch = ceil_div(N, JCH);
+    const int64_t per = JS_THREADS / 256 / nch;  // >= 32: nch <= 2^18
+    for (int64_t a = lo; a < hi; a += per) {
+        const int64_t nb = hi - a < per ? hi - a : per;
+        hipLaunchKernelGGL(jaccard_self_kernel<PASS>, dim3((unsigned)(nb * nch)), dim3(256), 0, s, N, a, nch, Vq, irow,
+                           ival, cbnd, eps, core, counts, parent, border, out ? out + (a - lo) * ldo : nullptr, ldo);
+        RM_LAUNCHED();
+    }
+    return OK;
+}
+
+// workspace of reidmi_dbscan_jaccard: the O(N) state (cluster.h) | the chunk bounds
+static bool dbs_jaccard_ws(int64_t N, DbsState* w, int64_t* bytes) {
+    if (!dbs_state(N, w)) return false;
+    *bytes = w->bytes + jaccard_bounds_bytes(N, N);
+    return true;
 }
 
 }  // namespace reidmi
@@ -348,4 +496,70 @@ REIDMI_API int reidmi_rr_jaccard_topk_rows(const float* feat, int64_t N, int64_t
         RM_LAUNCHED();
     }
     return OK;
+}
+
+REIDMI_API int reidmi_rr_jaccard_self_rows(int64_t N, int64_t lo, int64_t hi, const int64_t* qoff, const int32_t* qcol,
+                                           const uint16_t* qval, const int64_t* coff, const int32_t* irow,
+                                           const uint16_t* ival, uint16_t* out, int64_t ldo, void* bounds,
+                                           int64_t bounds_bytes, void* stream) {
+    RM_REQUIRE(N >= 1 && N < (1ll << 31) && 0 <= lo && lo <= hi && hi <= N && ldo >= N,
+               "rr_jaccard_self_rows: bad shape or row range (need 1 <= N < 2^31, 0 <= lo <= hi <= N, ldo >= N)");
+    RM_REQUIRE(qoff && qcol && qval && coff && irow && ival && out, "rr_jaccard_self_rows: inputs and out required");
+    RM_REQUIRE(bounds && ((uintptr_t)bounds & 7) == 0 && bounds_bytes >= jaccard_bounds_bytes(N, N),
+               "rr_jaccard_self_rows: bounds of reidmi_rr_jaccard_bounds_bytes(N, N) bytes (8-byte aligned) required");
+    if (hi == lo) return OK;
+    hipStream_t s = (hipStream_t)stream;
+    int64_t* cbnd = (int64_t*)bounds;
+    int rc;
+    if ((rc = jaccard_self_bounds(N, coff, irow, cbnd, s))) return rc;
+    return jaccard_self_run<JS_ROWS>(N, lo, hi, csr_rows(qoff, qcol, qval), irow, ival, cbnd, 0.0f, nullptr, nullptr,
+                                     nullptr, nullptr, out, ldo, s);
+}
+
+REIDMI_API int64_t reidmi_dbscan_jaccard_workspace_bytes(int64_t N) {
+    DbsState w;
+    int64_t bytes;
+    return dbs_jaccard_ws(N, &w, &bytes) ? bytes : -1;
+}
+
+// The passes of cluster.hip with the distance replaced: count, init, union, compress, border,
+// labels; eps in fp16, as jd is.
+REIDMI_API int reidmi_dbscan_jaccard(int64_t N, const int64_t* qoff, const int32_t* qcol, const uint16_t* qval,
+                                     const int64_t* coff, const int32_t* irow, const uint16_t* ival, float eps,
+                                     int min_samples, int32_t* labels, int32_t* counts, uint8_t* core,
+                                     int32_t* n_clusters, void* ws, int64_t ws_bytes, void* stream) {
+    RM_REQUIRE(N >= 1 && N < (1ll << 31), "dbscan_jaccard: bad shape (need 1 <= N < 2^31)");
+    RM_REQUIRE(eps >= 0.0f && eps <= 3.402823466e+38f, "dbscan_jaccard: eps must be finite and >= 0");
+    const float eps16 = (float)(_Float16)eps;  // round to nearest even, as numpy's float16(eps)
+    RM_REQUIRE(eps16 < 1.0f, "dbscan_jaccard: eps must round to less than 1 in fp16 (jd = 1: no shared column)");
+    RM_REQUIRE(min_samples >= 1, "dbscan_jaccard: need min_samples >= 1");
+    RM_REQUIRE(qoff && qcol && qval && coff && irow && ival, "dbscan_jaccard: V_qe rows and their inverted index required");
+    RM_REQUIRE(labels != nullptr && counts != nullptr && core != nullptr && n_clusters != nullptr,
+               "dbscan_jaccard: labels, counts, core and n_clusters required");
+    DbsState w;
+    int64_t bytes;
+    RM_REQUIRE(dbs_jaccard_ws(N, &w, &bytes) && ws != nullptr && ((uintptr_t)ws & 15) == 0 && ws_bytes >= bytes,
+               "dbscan_jaccard: workspace (reidmi_dbscan_jaccard_workspace_bytes, 16-byte aligned) required");
+    hipStream_t s = (hipStream_t)stream;
+    int32_t* parent = (int32_t*)((char*)ws + w.parent_off);
+    int32_t* border = (int32_t*)((char*)ws + w.border_off);
+    int32_t* number = (int32_t*)((char*)ws + w.number_off);
+    int32_t* bsum = (int32_t*)((char*)ws + w.bsum_off);
+    int64_t* cbnd = (int64_t*)((char*)ws + w.bytes);
+    const Rows Vq = csr_rows(qoff, qcol, qval);
+    int rc;
+    RM_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)N * 4, s));
+    if ((rc = jaccard_self_bounds(N, coff, irow, cbnd, s))) return rc;
+    if ((rc = jaccard_self_run<DBS_COUNT>(N, 0, N, Vq, irow, ival, cbnd, eps16, core, counts, parent, border, nullptr,
+                                          0, s)))
+        return rc;
+    if ((rc = dbs_init_launch(counts, N, min_samples, core, parent, border, s))) return rc;
+    if ((rc = jaccard_self_run<DBS_UNION>(N, 0, N, Vq, irow, ival, cbnd, eps16, core, counts, parent, border, nullptr,
+                                          0, s)))
+        return rc;
+    if ((rc = dbs_compress_launch(parent, N, s))) return rc;
+    if ((rc = jaccard_self_run<DBS_BORDER>(N, 0, N, Vq, irow, ival, cbnd, eps16, core, counts, parent, border, nullptr,
+                                           0, s)))
+        return rc;
+    return dbs_labels_launch(core, parent, border, number, bsum, w.nb, N, n_clusters, labels, s);
 }
