@@ -34,7 +34,8 @@ const char* reidmi_last_error(void);
  * 8: reidmi_eval_feat_f32 and the reidmi_evf_* stages added.
  * 9: reidmi_search_bounded_f32 added.
  * 10: reidmi_dbscan_f32 added.
- * 11: reidmi_rr_jaccard_self_rows and reidmi_dbscan_jaccard added. */
+ * 11: reidmi_rr_jaccard_self_rows and reidmi_dbscan_jaccard added.
+ * 12: reidmi_pair_stats_f32 added. */
 int reidmi_abi_version(void);
 
 /* ------------------------------------------------------------ retrieval back end */
@@ -258,6 +259,60 @@ int64_t reidmi_dbscan_workspace_bytes(int64_t N, int64_t D);
 int reidmi_dbscan_f32(const float* x, int64_t N, int64_t D, int64_t ldx, float eps, int min_samples,
                       int32_t* labels, int32_t* counts, uint8_t* core, int32_t* n_clusters, void* ws,
                       int64_t ws_bytes, void* stream);
+
+/* Verification and open-set statistics of a labelled split from the features: the histogram of the
+ * genuine and of the impostor distances under the caller's edges, and every query's nearest genuine
+ * and nearest impostor item.  No Q x G matrix is formed and the workspace is linear in Q.  These
+ * are what TAR@FAR, EER, the open-set detection-and-identification rate and the choice of
+ * reidmi_search_bounded_f32's radius or reidmi_dbscan_f32's eps are computed from.
+ * Distance: d(i, j) is reidmi_distmat_f32's of q against g, bit for bit (the SQUARED Euclidean
+ * distance); the same D, pitches and alignments are accepted (rows that are not 16-byte aligned,
+ * or D % 4 != 0, run the single-stage mainloop).  Features must be finite.
+ * Classes of the pair (i, j):
+ *   removed   q_cams / g_cams given and g_pids[j] == q_pids[i] && g_cams[j] == q_cams[i]
+ *             (evaluate.py:46-48); and, with self_base >= 0, the pair with i == self_base + j (the
+ *             diagonal of a set compared with itself, also when the set arrives in blocks: self_base
+ *             is then the number of rows before this block; -1: no such pair).  Counted nowhere.
+ *   genuine   g_pids[j] == q_pids[i], not removed
+ *   impostor  g_pids[j] != q_pids[i], not removed
+ * q_pids and g_pids are required; q_cams and g_cams are both given or both NULL (nothing is removed
+ * for its camera then).
+ * Histogram: edges is a HOST array of 1 <= n_edges <= 255 finite, non-decreasing fp32 values.  It is
+ * checked and read during the call (it may be freed afterwards) and reaches the kernel by value in
+ * its arguments: no copy, no synchronisation.  The bin of a pair is b = #{t : edges[t] < d}, which
+ * is np.searchsorted(edges, d, side="left"): bins 0 .. n_edges, and hist[0] + ... + hist[t] is the
+ * number of pairs with d <= edges[t], the pairs a radius or an eps of edges[t] admits.  The call
+ * ADDS the genuine pairs' bins to hist_pos and the impostor pairs' to hist_neg (device uint64
+ * [n_edges + 1] each; the caller zeroes them before the first block).  No counter can overflow: a
+ * workgroup counts in 32-bit LDS bins, a 128 x 128 tile adds at most 2^14 to one, and the bins are
+ * added to the 64-bit global counters (one add per non-empty bin) and cleared at the end of the
+ * workgroup's gallery range and after every 2^17 tiles, so none exceeds 2^31; a global counter
+ * holds up to 2^64 - 1 and one call adds fewer than 2^62 pairs.
+ * Nearest items: near_pos_* of query i is its nearest genuine item, near_neg_* its nearest impostor,
+ * in the order of the rank lists: the smaller d by fp32 `<`, ties by the smaller global index
+ * index_base + j; -0.0 ties with +0.0 (and is reported as +0.0; the distance never is -0.0).  The
+ * arrays are in/out (device fp32 / int32 [Q]; the caller starts them at +inf / -1, which stands for
+ * "no item"): the call lowers a row's (dist, idx) only to a smaller key.  Inside, a workgroup keeps
+ * one packed 64-bit key (the distance's bits in an order-preserving form, then the index) per row
+ * in LDS, the ranges meet in a 64-bit minimum in the workspace, and a per-row kernel merges that
+ * into the in/out arrays.
+ * Sums of integers and minima of unique keys: hist_* and near_* are the same for any cut of the
+ * gallery into blocks or shards, any order of the blocks and any scheduling.
+ * Geometry: reidmi_evf_count's (a workgroup per 128-row query band and contiguous gallery range, at
+ * most 1024 workgroups unless Q > 131072, four per CU).
+ * ws: reidmi_pair_stats_workspace_bytes(Q, G) bytes, 16-byte aligned: the Q + G squared norms and
+ * 16 bytes per query (negative on bad shapes).
+ * Refused with REIDMI_EINVAL before any HIP call: Q < 0, G < 1, D < 1, Q or G >= 2^31; a pitch < D;
+ * n_edges outside [1, 255]; NULL, non-finite or decreasing edges; a missing pid array; one camera
+ * array without the other; index_base < 0 or index_base + G > 2^31 - 1; self_base < -1; a NULL
+ * output; a NULL, misaligned or short workspace; NULL features.  Q = 0 is a no-op.  No allocation
+ * or synchronisation inside. */
+int64_t reidmi_pair_stats_workspace_bytes(int64_t Q, int64_t G);
+int reidmi_pair_stats_f32(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G, int64_t ldg, int64_t D,
+                          const int64_t* q_pids, const int64_t* q_cams, const int64_t* g_pids, const int64_t* g_cams,
+                          const float* edges, int n_edges, int64_t index_base, int64_t self_base,
+                          uint64_t* hist_pos, uint64_t* hist_neg, float* near_pos_dist, int32_t* near_pos_idx,
+                          float* near_neg_dist, int32_t* near_neg_idx, void* ws, int64_t ws_bytes, void* stream);
 
 
 /* k-reciprocal re-ranking — re_ranking(probFea, galFea, k1, k2, lambda_value) (reranking.py:29-100),

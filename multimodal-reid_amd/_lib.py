@@ -20,7 +20,7 @@ TOOLS_LIB_PATH = os.path.join(PKG, "libreidmi_tools.so")  # tests / A-B tools on
 
 _SCALARS = {"int": ctypes.c_int, "int32_t": ctypes.c_int, "int64_t": ctypes.c_int64, "float": ctypes.c_float,
             "double": ctypes.c_double, "uint16_t": ctypes.c_uint16}
-_POINTEES = ("void", "char", "uint8_t")  # known only behind a pointer
+_POINTEES = ("void", "char", "uint8_t", "uint64_t")  # known only behind a pointer
 _RESULTS = {"int": ctypes.c_int, "int64_t": ctypes.c_int64, "char*": ctypes.c_char_p}
 
 _LIB = None

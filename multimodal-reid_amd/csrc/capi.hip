@@ -22,5 +22,6 @@ REIDMI_API const char* reidmi_last_error(void) { return reidmi::g_err.c_str(); }
 // 9: bounded search (reidmi_search_bounded_f32);
 // 10: clustering (reidmi_dbscan_f32);
 // 11: clustering on the k-reciprocal Jaccard distance (reidmi_rr_jaccard_self_rows,
-//     reidmi_dbscan_jaccard).
-REIDMI_API int reidmi_abi_version(void) { return 11; }
+//     reidmi_dbscan_jaccard);
+// 12: pair statistics (reidmi_pair_stats_f32).
+REIDMI_API int reidmi_abi_version(void) { return 12; }

@@ -7,6 +7,10 @@ and error behaviour, computed by libreidmi HIP kernels on the GPU.
                                    -> (cmc np.float32[max_rank], mAP np.float64)   evaluate.py:29-88
     R1_mAP_eval(num_query, max_rank=50, feat_norm=True, reranking=False)           evaluate.py:91-135
 
+Verification and open-set statistics of a labelled split, from the features (reidmi_pair_stats_f32):
+pair_stats, pair_stats_blocks, merge_pair_stats, PairStatsAccumulator, R1_mAP_eval.pair_stats, and on
+their result verification_curve, threshold_at_far, tar_at_far, equal_error_rate, open_set_rates.
+
 Beyond the reference: ranked search (search, search_blocks, search_sharded), and the step
 between "the k nearest" and "the features I rank with" as one kernel (reidmi_combine_rows_f32):
 expand_features (AQE / alpha-QE), database_augmentation (DBA), pool_features (multi-query and
@@ -21,6 +25,8 @@ Tie semantics: ranks inside groups of exactly equal distances are ordered by gal
 index (np.argsort(kind="stable")); the reference's unstable argsort orders such groups
 in a host-dependent way.
 """
+import ctypes
+
 import numpy as np
 import torch
 
@@ -779,6 +785,279 @@ def mean_inp(valid, last, npos):
     return np.mean(npos[v].astype(np.float64) / (last[v].astype(np.float64) + 1.0))
 
 
+# ------------------------------- verification / open-set statistics (reidmi_pair_stats_f32)
+PAIR_STATS_MAX_EDGES = 255
+
+
+def default_edges():
+    """255 equal steps over [0, 4], the range of squared distances between unit vectors."""
+    return (np.arange(1, PAIR_STATS_MAX_EDGES + 1, dtype=np.float64) * (4.0 / PAIR_STATS_MAX_EDGES)).astype(np.float32)
+
+
+def _edges(what, edges):
+    """edges as a contiguous host fp32 array, checked as the library checks it."""
+    if edges is None:
+        return default_edges()
+    if isinstance(edges, torch.Tensor):
+        edges = edges.detach().cpu().numpy()
+    try:
+        e = np.ascontiguousarray(np.asarray(edges, dtype=np.float32)).reshape(-1)
+    except (TypeError, ValueError):
+        raise _lib.ReidmiError(f"{what}: edges must be a 1-D array of numbers") from None
+    if not 1 <= e.size <= PAIR_STATS_MAX_EDGES:
+        raise _lib.ReidmiError(f"{what}: need 1 <= len(edges) <= {PAIR_STATS_MAX_EDGES}, not {e.size}")
+    if not np.isfinite(e).all():
+        raise _lib.ReidmiError(f"{what}: edges must be finite")
+    if (e[1:] < e[:-1]).any():
+        raise _lib.ReidmiError(f"{what}: edges must be non-decreasing")
+    return e
+
+
+class PairStats:
+    """The statistics of a labelled split (reidmi_pair_stats_f32, include/reidmi.h):
+        edges      host fp32 [E]
+        hist_pos   int64 [E + 1]: genuine pairs per bin, bin = np.searchsorted(edges, d, side="left")
+        hist_neg   int64 [E + 1]: impostor pairs per bin
+        near_pos   (dist fp32 [Q], idx int32 [Q]): every query's nearest genuine item, +inf / -1 without one
+        near_neg   likewise, the nearest impostor
+    The arrays are device tensors (pair_stats_device) or numpy arrays (pair_stats, .numpy())."""
+
+    def __init__(self, edges, hist_pos, hist_neg, near_pos, near_neg):
+        self.edges, self.hist_pos, self.hist_neg = edges, hist_pos, hist_neg
+        self.near_pos, self.near_neg = tuple(near_pos), tuple(near_neg)
+
+    def numpy(self):
+        def host(a):
+            return a.cpu().numpy() if isinstance(a, torch.Tensor) else np.asarray(a)
+        return PairStats(self.edges, host(self.hist_pos), host(self.hist_neg), tuple(host(a) for a in self.near_pos),
+                         tuple(host(a) for a in self.near_neg))
+
+
+class PairStatsAccumulator:
+    """pair_stats_device over a gallery that arrives in blocks: add() each block (a device or host
+    tensor, or a numpy array; a host block is on the device for the call only), then result().  The
+    counts are integer sums and the nearest items minima of unique (distance, global index) keys, so
+    the result is bit for bit the one-call result for every way of cutting the gallery and every order
+    of the blocks.  q_camids None: every block comes without g_camids and nothing is removed for its
+    camera.  A block's rows stand at the global indices index_base .. index_base + rows: by default
+    the number of rows added before it (the blocks in gallery order); a caller that feeds them in
+    another order passes each block's own index_base.  exclude_self: the gallery is the query set
+    itself, and the pair of a row with itself (global index == query row) is left out.
+    Carried state: two histograms and two [Q] (dist, idx) pairs; nothing grows with the gallery."""
+
+    def __init__(self, qf, q_pids, q_camids=None, edges=None, exclude_self=False):
+        if not isinstance(exclude_self, (bool, np.bool_)):
+            raise _lib.ReidmiError("PairStatsAccumulator: exclude_self must be True or False")
+        self.edges = _edges("PairStatsAccumulator", edges)
+        if q_pids is None:
+            raise _lib.ReidmiError("PairStatsAccumulator: q_pids are required")
+        if isinstance(qf, (np.ndarray, torch.Tensor)) and qf.ndim != 2:
+            raise _lib.ReidmiError("PairStatsAccumulator: qf must be [Q][D]")
+        self.qf = _as_dev_f32(qf)
+        Q, dev = self.qf.shape[0], self.qf.device
+        self.qp = _as_dev_i64(q_pids)
+        self.cams = q_camids is not None
+        self.qc = _as_dev_i64(q_camids) if self.cams else None
+        if self.qp.numel() != Q or (self.cams and self.qc.numel() != Q):
+            raise _lib.ReidmiError("PairStatsAccumulator: one label per query row")
+        self.exclude_self = bool(exclude_self)
+        E = self.edges.size
+        self.hist_pos = torch.zeros(E + 1, device=dev, dtype=torch.int64)  # the library's uint64 counters
+        self.hist_neg = torch.zeros(E + 1, device=dev, dtype=torch.int64)
+        self.pos_dist = torch.full((Q,), float("inf"), device=dev, dtype=torch.float32)
+        self.neg_dist = torch.full((Q,), float("inf"), device=dev, dtype=torch.float32)
+        self.pos_idx = torch.full((Q,), -1, device=dev, dtype=torch.int32)
+        self.neg_idx = torch.full((Q,), -1, device=dev, dtype=torch.int32)
+        self.count = 0  # gallery items added so far
+
+    def add(self, gf_block, g_pids, g_camids=None, index_base=None):
+        if (g_camids is not None) != self.cams:
+            raise _lib.ReidmiError("PairStatsAccumulator.add: gallery cameras go with query cameras: every block has "
+                                   "them or none has")
+        if g_pids is None:
+            raise _lib.ReidmiError("PairStatsAccumulator.add: g_pids are required")
+        rows = int(gf_block.shape[0])
+        base = self.count if index_base is None else int(index_base)
+        if base < 0 or base + rows > 2 ** 31 - 1:
+            raise _lib.ReidmiError("PairStatsAccumulator.add: gallery indices must fit int32 "
+                                   "(index_base >= 0, index_base + rows <= 2^31 - 1)")
+        if rows == 0:
+            return
+        gf = _as_dev_f32(gf_block)
+        Q, D = self.qf.shape
+        if gf.dim() != 2 or gf.shape[1] != D:
+            raise _lib.ReidmiError(f"PairStatsAccumulator.add: a block must be [rows][{D}]")
+        gp = _as_dev_i64(g_pids)
+        gc = _as_dev_i64(g_camids) if self.cams else None
+        if gp.numel() != rows or (self.cams and gc.numel() != rows):
+            raise _lib.ReidmiError("PairStatsAccumulator.add: one label per gallery row")
+        nb = _lib.load().reidmi_pair_stats_workspace_bytes(Q, rows)
+        ws = torch.empty(max(nb, 16), device=self.qf.device, dtype=torch.uint8)
+        _lib.call("reidmi_pair_stats_f32", _lib.ptr(self.qf), Q, self.qf.stride(0), _lib.ptr(gf), rows, gf.stride(0), D,
+                  _lib.ptr(self.qp), _lib.ptr(self.qc), _lib.ptr(gp), _lib.ptr(gc),
+                  ctypes.c_void_p(self.edges.ctypes.data), int(self.edges.size), base,
+                  base if self.exclude_self else -1, _lib.ptr(self.hist_pos), _lib.ptr(self.hist_neg),
+                  _lib.ptr(self.pos_dist), _lib.ptr(self.pos_idx), _lib.ptr(self.neg_dist), _lib.ptr(self.neg_idx),
+                  _lib.ptr(ws), nb, _lib.stream())
+        self.count += rows
+
+    def result(self):
+        """A PairStats of device tensors."""
+        if self.count == 0:
+            raise _lib.ReidmiError("PairStatsAccumulator: the gallery is empty")
+        return PairStats(self.edges, self.hist_pos, self.hist_neg, (self.pos_dist, self.pos_idx),
+                         (self.neg_dist, self.neg_idx))
+
+
+def pair_stats_device(qf, gf, q_pids, g_pids, q_camids=None, g_camids=None, edges=None, exclude_self=False,
+                      index_base=0):
+    """The genuine / impostor distance histograms and every query's nearest genuine and nearest
+    impostor item, from the features (reidmi_pair_stats_f32: counted in the distance kernel's
+    epilogue, no (Q, G) matrix): a PairStats of device tensors.  The distance is
+    euclidean_distance_device's, bit for bit.  A pair is genuine when the pids are equal, impostor
+    when they differ; with q_camids / g_camids (both or neither) the gallery items of the query's pid
+    and camera are removed (evaluate.py:46-48) and counted nowhere.  edges: up to 255 finite,
+    non-decreasing thresholds (None: default_edges()); hist[0..t].sum() is the number of pairs at a
+    distance <= edges[t], the pairs search(max_dist=edges[t]) and cluster.dbscan(eps=edges[t]) admit.
+    exclude_self: gf is qf itself, and the pair of a row with itself is left out.  index_base: the
+    global index of gf's first row (a gallery shard; merge_pair_stats joins the shards' results)."""
+    acc = PairStatsAccumulator(qf, q_pids, q_camids, edges, exclude_self)
+    if int(gf.shape[0]) < 1:
+        raise _lib.ReidmiError("pair_stats: the gallery is empty")
+    acc.add(gf, g_pids, g_camids, index_base)
+    return acc.result()
+
+
+def pair_stats(qf, gf, q_pids, g_pids, q_camids=None, g_camids=None, edges=None, exclude_self=False, index_base=0):
+    """pair_stats_device, returned as numpy arrays."""
+    return pair_stats_device(qf, gf, q_pids, g_pids, q_camids, g_camids, edges, exclude_self, index_base).numpy()
+
+
+def pair_stats_blocks_device(qf, blocks, q_pids, q_camids=None, edges=None, exclude_self=False):
+    """PairStatsAccumulator over ``blocks``: an iterable of (features, g_pids) or (features, g_pids,
+    g_camids) tuples in gallery order.  Bit for bit pair_stats_device over their concatenation."""
+    acc = PairStatsAccumulator(qf, q_pids, q_camids, edges, exclude_self)
+    for b in blocks:
+        acc.add(*b)
+    return acc.result()
+
+
+def pair_stats_blocks(qf, blocks, q_pids, q_camids=None, edges=None, exclude_self=False):
+    """pair_stats_blocks_device, returned as numpy arrays."""
+    return pair_stats_blocks_device(qf, blocks, q_pids, q_camids, edges, exclude_self).numpy()
+
+
+def merge_pair_stats(a, b):
+    """The statistics of two gallery parts (blocks, or the shards of several ranks: what they would
+    exchange) as one: the histograms added, and per query the smaller (distance, global index) key of
+    the two nearest items; an entry without an item (-1) loses to any item.  Both parts must use the
+    same edges, the same queries and one global index space (pair_stats_device(index_base=)).  Device
+    or numpy PairStats, both of one kind; the result is of that kind."""
+    if not isinstance(a, PairStats) or not isinstance(b, PairStats):
+        raise _lib.ReidmiError("merge_pair_stats: two PairStats are required")
+    if a.edges.shape != b.edges.shape or not np.array_equal(a.edges.view(np.uint32), b.edges.view(np.uint32)):
+        raise _lib.ReidmiError("merge_pair_stats: the two results were counted under different edges")
+    dev = isinstance(a.hist_pos, torch.Tensor)
+    if dev != isinstance(b.hist_pos, torch.Tensor):
+        raise _lib.ReidmiError("merge_pair_stats: pass two device results or two numpy results")
+    if tuple(a.near_pos[0].shape) != tuple(b.near_pos[0].shape):
+        raise _lib.ReidmiError("merge_pair_stats: the two results have different numbers of queries")
+    where = torch.where if dev else np.where
+
+    def nearest(x, y):
+        (xd, xi), (yd, yi) = x, y
+        take_y = (yi >= 0) & ((xi < 0) | (yd < xd) | ((yd == xd) & (yi < xi)))
+        return where(take_y, yd, xd), where(take_y, yi, xi)
+
+    return PairStats(a.edges, a.hist_pos + b.hist_pos, a.hist_neg + b.hist_neg, nearest(a.near_pos, b.near_pos),
+                     nearest(a.near_neg, b.near_neg))
+
+
+def _host_stats(stats):
+    if not isinstance(stats, PairStats):
+        raise _lib.ReidmiError("a PairStats (pair_stats / pair_stats_device) is required")
+    return stats.numpy()
+
+
+def _ratio(num, den):
+    """num / den in float64; NaN where den is 0 (an empty class)."""
+    num = np.asarray(num, dtype=np.float64)
+    return num / den if den > 0 else np.full(num.shape, np.nan)
+
+
+def verification_curve(stats):
+    """(far, tar) float64 [E]: at the threshold edges[t], the share of the impostor pairs and of the
+    genuine pairs with a distance <= edges[t] (the false accept rate and the true accept rate of
+    "same identity iff d <= edges[t]").  A class without pairs gives NaN."""
+    s = _host_stats(stats)
+    neg, pos = s.hist_neg.astype(np.int64), s.hist_pos.astype(np.int64)
+    return _ratio(np.cumsum(neg)[:-1], int(neg.sum())), _ratio(np.cumsum(pos)[:-1], int(pos.sum()))
+
+
+def _target(what, far):
+    far = float(far)
+    if not 0.0 <= far <= 1.0:
+        raise _lib.ReidmiError(f"{what}: the target false accept rate must lie in [0, 1]")
+    return far
+
+
+def threshold_at_far(stats, far):
+    """The largest edge whose false accept rate is at or below ``far`` (float; the edges are the only
+    thresholds the histogram knows).  NaN when even the first edge accepts more, or without
+    impostor pairs."""
+    target = _target("threshold_at_far", far)
+    s = _host_stats(stats)
+    f, _ = verification_curve(s)
+    ok = np.nonzero(f <= target)[0]
+    return float(s.edges[ok[-1]]) if ok.size else float("nan")
+
+
+def tar_at_far(stats, far):
+    """The true accept rate at threshold_at_far(stats, far); NaN when that is NaN or without
+    genuine pairs."""
+    target = _target("tar_at_far", far)
+    f, t = verification_curve(stats)
+    ok = np.nonzero(f <= target)[0]
+    return float(t[ok[-1]]) if ok.size else float("nan")
+
+
+def equal_error_rate(stats):
+    """The rate at which the false accept rate and the false reject rate 1 - TAR cross, both
+    interpolated linearly between the two neighbouring edges that bracket the crossing (below the
+    first edge the curve starts at FAR 0 / FRR 1, above the last it ends at FAR 1 / FRR 0).  NaN
+    when a class has no pairs."""
+    f, t = verification_curve(stats)
+    if np.isnan(f).any() or np.isnan(t).any():
+        return float("nan")
+    far = np.concatenate([[0.0], f, [1.0]])
+    frr = np.concatenate([[1.0], 1.0 - t, [0.0]])
+    k = int(np.nonzero(far - frr >= 0.0)[0][0])  # >= 1: far - frr starts at -1 and ends at +1
+    f0, f1, r0, r1 = far[k - 1], far[k], frr[k - 1], frr[k]
+    s = (r0 - f0) / ((f1 - f0) - (r1 - r0))  # the denominator is (f1 - r1) - (f0 - r0) > 0
+    return float(f0 + s * (f1 - f0))
+
+
+def open_set_rates(stats, thresholds):
+    """(dir, far) float64 arrays shaped like ``thresholds``: the open-set detection-and-identification
+    rate and the false alarm rate of rank-1 identification under a distance threshold.  A query is
+    known when the gallery holds a genuine item for it (near_pos idx >= 0).  A known query is
+    identified at tau iff its nearest genuine item comes before its nearest impostor in the order
+    of the rank lists (distance, then global index: what search puts first) and lies within tau;
+    DIR(tau) is their share of the known queries.  An unknown query raises a false alarm iff its
+    nearest impostor lies within tau; FAR(tau) is their share of the unknown queries.  A class
+    without queries gives NaN."""
+    s = _host_stats(stats)
+    tau = np.asarray(thresholds, dtype=np.float64)
+    (pd, pi), (nd, ni) = s.near_pos, s.near_neg
+    known = pi >= 0
+    first = known & ((ni < 0) | (pd < nd) | ((pd == nd) & (pi < ni)))
+    t = tau.reshape(-1, 1)
+    hit = (first[None, :] & (pd[None, :].astype(np.float64) <= t)).sum(1)
+    alarm = ((~known & (ni >= 0))[None, :] & (nd[None, :].astype(np.float64) <= t)).sum(1)
+    return (_ratio(hit, int(known.sum())).reshape(tau.shape),
+            _ratio(alarm, int((~known).sum())).reshape(tau.shape))
+
+
 # ------------------------------------------------------------ reference surface
 def euclidean_distance(qf, gf):
     """evaluate.py:7-13 — returns a numpy float32 (Q,G) matrix."""
@@ -979,6 +1258,31 @@ class R1_mAP_eval():
                 from .reranking import re_ranking_search
                 return re_ranking_search(feats[:nq], feats[nq:], k, 50, 15, 0.3, *lab)
             return search(feats[:nq], feats[nq:], k, *lab)
+
+    def pair_stats(self, edges=None):
+        """pair_stats (numpy) of the query rows against the gallery rows on the features and labels
+        compute() scores: after the normalisation and the query expansion / database augmentation,
+        with the same-pid-same-camera removal.  The thresholds read off it (threshold_at_far) are on
+        the scale of rank_lists' distances, search(max_dist=) and cluster.dbscan(eps=).  Not with
+        ``sharded=True`` (the ranks would have to exchange their statistics: merge_pair_stats joins
+        them, a collective wrapper does not exist yet) and not with ``reranking=True`` (the re-ranked
+        distance has no feature form): ReidmiError."""
+        if self.sharded:
+            raise _lib.ReidmiError("R1_mAP_eval.pair_stats is not available with sharded=True (no collective "
+                                   "wrapper yet: compute pair_stats per shard and join them with merge_pair_stats)")
+        if self.reranking:
+            raise _lib.ReidmiError("R1_mAP_eval.pair_stats is not available with reranking=True (the re-ranked "
+                                   "distance has no feature form)")
+        from . import distributed as rd
+        self._check_expansion()
+        feats = torch.cat(self.feats, dim=0)
+        if self.feat_norm:
+            feats = l2_normalize_device(feats)
+        nq = self.num_query
+        pids, camids = np.asarray(self.pids), np.asarray(self.camids)
+        with rd.local():
+            feats = self._expand(feats)
+            return pair_stats(feats[:nq], feats[nq:], pids[:nq], pids[nq:], camids[:nq], camids[nq:], edges)
 
     @staticmethod
     def _print(cmc, mAP):
