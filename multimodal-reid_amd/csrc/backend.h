@@ -1,7 +1,7 @@
 // backend.h — the retrieval back end's internal launchers that another source calls, grouped by
 // the file that defines them (internal, not part of the C ABI).  Callers: the distance launchers
 // from rerank.hip (one-call R1), rerank_rank.hip (R2 chunks) and rerank_jaccard.hip (od chunks),
-// the row norms from search.hip and evalfeat.hip; topk_launch from rerank.hip and rerank_rank.hip;
+// the row norms from distance.h's dm_norms and cluster.hip; topk_launch from rerank.hip and rerank_rank.hip;
 // evalfeat.hip its last stage; prefilter.hip's from rerank_rank.hip alone.  The re-rank sources'
 // own cross-file launchers are in rerank.h.
 #pragma once

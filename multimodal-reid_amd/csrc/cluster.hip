@@ -23,13 +23,9 @@
 
 namespace reidmi {
 
-constexpr int DBS_SLOTS = 1024;                      // 256 CUs x DM2_MINWG
-constexpr int DBS_SMEM = 2 * 2 * DM2_BK * DM2_LD;    // floats: both mainloops' stages
-static_assert(DBS_SMEM >= 2 * DM_BK * (DM_BM + DM_PAD), "dbs_tile: both mainloops' stages fit");
-
-// evf_count_kernel's structure: a workgroup owns one 128-row band and one contiguous column range
-// [c0, c1) and walks it in 128-column tiles.  Row state in LDS.  LDS: 33 024 B of operand stages
-// + 1.5 KB of row state: four workgroups per CU.
+// distance.h's band-and-range walk: a workgroup owns one 128-row band and one contiguous column
+// range [c0, c1) and walks it in 128-column tiles.  Row state in LDS.  LDS: 33 024 B of operand
+// stages + 1.5 KB of row state: four workgroups per CU.
 //   COUNT   every lane keeps the count of one row of its wave's quadrant (32 rows per half-wave,
 //           32 lanes per half-wave) in one register: the hits of a row are the set bits of its
 //           half of a ballot.  One LDS add per lane and one global add per row at the range's end.
@@ -44,17 +40,14 @@ __global__ __launch_bounds__(256, DM2_MINWG) void dbs_tile_kernel(
     const float* __restrict__ x, const float* __restrict__ xx, int64_t N, int64_t D, int64_t ldx, int64_t range_len,
     float eps, const uint8_t* __restrict__ core, int32_t* __restrict__ counts, int32_t* parent,
     int32_t* __restrict__ border) {
-    __shared__ float smem[DBS_SMEM];
+    __shared__ float smem[DM_SMEM];
     __shared__ float s_xx[DM_BM];
     __shared__ int s_row[DM_BM];  // COUNT: hits; UNION / BORDER: the row takes part
     __shared__ int s_min[DM_BM];  // BORDER: smallest root so far
     const DmThread t = dm_thread();
     const int tid = t.tid, lane = t.lane, wm = t.wm, wn = t.wn;
-    // band fastest: the bands of one column range run side by side on one XCD and share its tiles
-    const int64_t bands = (N + DM_BM - 1) / DM_BM;
-    const int64_t wg = xcd_contiguous_wg();
-    const int64_t band = wg % bands, split = wg / bands, bm = band * DM_BM;
-    const int64_t c0 = split * range_len, c1 = c0 + range_len < N ? c0 + range_len : N;
+    const DmWalk w = dm_walk(N, N, range_len);
+    const int64_t bm = w.bm, c0 = w.c0, c1 = w.c1;
     bool mine = false;
     if (tid < DM_BM) {
         const bool in = bm + tid < N;
@@ -76,13 +69,7 @@ __global__ __launch_bounds__(256, DM2_MINWG) void dbs_tile_kernel(
         }
         f32x16 acc[2][2];
         dm_acc_zero(acc);
-        if constexpr (PIPE)
-            dm_tile_pipe(t, x, x, N, c1, D, ldx, ldx, bm, bn, (float(*)[DM2_BK][DM2_LD])smem,
-                         (float(*)[DM2_BK][DM2_LD])(smem + 2 * DM2_BK * DM2_LD), acc);
-        else
-            dm_tile_single(t, x, x, N, c1, D, ldx, ldx, bm, bn, (float(*)[DM_BM + DM_PAD])smem,
-                           (float(*)[DM_BN + DM_PAD])(smem + DM_BK * (DM_BM + DM_PAD)), acc);
-        // both mainloops end on a barrier: the stages are free for the next tile
+        dm_tile<PIPE>(t, x, x, N, c1, D, ldx, ldx, bm, bn, smem, acc);
         int64_t j[2];
         float xxj[2];
         bool jok[2];
@@ -304,27 +291,22 @@ int dbs_labels_launch(const uint8_t* core, const int32_t* parent, const int32_t*
 // workspace: norms | the O(N) state (cluster.h)
 static bool dbs_ws(int64_t N, int64_t D, DbsState* w, int64_t* bytes) {
     if (D < 1 || !dbs_state(N, w)) return false;
-    *bytes = (N * 4 + 15) / 16 * 16 + w->bytes;
+    *bytes = dm_norm_bytes(N, 0) + w->bytes;
     return true;
 }
 
-// The column ranges of a pass: whole tiles, so that bands x S workgroups fill, and do not exceed,
-// the DBS_SLOTS resident workgroups (evalfeat.hip's evf_count_run).
+// The column ranges of a pass: distance.h's dm_walk_plan, the column tiles being the row bands.
 template <int PASS>
 static int dbs_pass_run(const float* x, const float* xx, int64_t N, int64_t D, int64_t ldx, float eps,
                         const uint8_t* core, int32_t* counts, int32_t* parent, int32_t* border, hipStream_t s) {
     const int64_t bands = (N + DM_BM - 1) / DM_BM;
-    int64_t s0 = DBS_SLOTS / bands;
-    s0 = s0 < 1 ? 1 : (s0 > bands ? bands : s0);
-    const int64_t per = (bands + s0 - 1) / s0, S = (bands + per - 1) / per, range_len = per * DM_BN;
+    int64_t S, range_len;
+    dm_walk_plan(bands, bands, &S, &range_len);
     RM_REQUIRE(bands * S < (1ll << 31), "dbscan: too many row bands for one launch");
     const dim3 grid((unsigned)(bands * S));
-    if (dm2_ok(x, ldx, x, ldx, D))
-        hipLaunchKernelGGL((dbs_tile_kernel<true, PASS>), grid, dim3(256), 0, s, x, xx, N, D, ldx, range_len, eps,
-                           core, counts, parent, border);
-    else
-        hipLaunchKernelGGL((dbs_tile_kernel<false, PASS>), grid, dim3(256), 0, s, x, xx, N, D, ldx, range_len, eps,
-                           core, counts, parent, border);
+    RM_BOOL_SWITCH(dm2_ok(x, ldx, x, ldx, D), PIPE,
+                   hipLaunchKernelGGL((dbs_tile_kernel<PIPE, PASS>), grid, dim3(256), 0, s, x, xx, N, D, ldx,
+                                      range_len, eps, core, counts, parent, border));
     RM_LAUNCHED();
     return OK;
 }
@@ -332,12 +314,6 @@ static int dbs_pass_run(const float* x, const float* xx, int64_t N, int64_t D, i
 }  // namespace reidmi
 
 using namespace reidmi;
-
-#define DBS_TRY(expr)              \
-    do {                           \
-        const int rc_ = (expr);    \
-        if (rc_ != OK) return rc_; \
-    } while (0)
 
 REIDMI_API int64_t reidmi_dbscan_workspace_bytes(int64_t N, int64_t D) {
     DbsState w;
@@ -369,10 +345,10 @@ REIDMI_API int reidmi_dbscan_f32(const float* x, int64_t N, int64_t D, int64_t l
     RM_CHECK_HIP(hipMemsetAsync(counts, 0, (size_t)N * 4, s));
     rows_sqnorm_launch(x, N, D, ldx, xx, s);
     RM_LAUNCHED();
-    DBS_TRY(dbs_pass_run<DBS_COUNT>(x, xx, N, D, ldx, eps, core, counts, parent, border, s));
-    DBS_TRY(dbs_init_launch(counts, N, min_samples, core, parent, border, s));
-    DBS_TRY(dbs_pass_run<DBS_UNION>(x, xx, N, D, ldx, eps, core, counts, parent, border, s));
-    DBS_TRY(dbs_compress_launch(parent, N, s));
-    DBS_TRY(dbs_pass_run<DBS_BORDER>(x, xx, N, D, ldx, eps, core, counts, parent, border, s));
+    RM_TRY(dbs_pass_run<DBS_COUNT>(x, xx, N, D, ldx, eps, core, counts, parent, border, s));
+    RM_TRY(dbs_init_launch(counts, N, min_samples, core, parent, border, s));
+    RM_TRY(dbs_pass_run<DBS_UNION>(x, xx, N, D, ldx, eps, core, counts, parent, border, s));
+    RM_TRY(dbs_compress_launch(parent, N, s));
+    RM_TRY(dbs_pass_run<DBS_BORDER>(x, xx, N, D, ldx, eps, core, counts, parent, border, s));
     return dbs_labels_launch(core, parent, border, number, bsum, w.nb, N, n_clusters, labels, s);
 }

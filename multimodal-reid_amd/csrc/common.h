@@ -29,6 +29,26 @@ int fail(int code, const std::string& msg);
 // After a launch: report launch-configuration errors immediately.
 #define RM_LAUNCHED() RM_CHECK_HIP(hipGetLastError())
 
+// A step that already reported its failure (fail()): pass its status on.
+#define RM_TRY(expr)                          \
+    do {                                      \
+        const int rc_ = (expr);               \
+        if (rc_ != ::reidmi::OK) return rc_;  \
+    } while (0)
+
+// Runs the statement with NAME a constant true or false by cond, so that a launch whose kernel
+// is chosen by a run-time flag, kernel<NAME>, writes its arguments once.  Nests.
+#define RM_BOOL_SWITCH(cond, NAME, ...)  \
+    do {                                 \
+        if (cond) {                      \
+            constexpr bool NAME = true;  \
+            __VA_ARGS__;                 \
+        } else {                         \
+            constexpr bool NAME = false; \
+            __VA_ARGS__;                 \
+        }                                \
+    } while (0)
+
 typedef __attribute__((ext_vector_type(8))) __bf16 bf16x8;
 typedef __attribute__((ext_vector_type(4))) __bf16 bf16x4;
 typedef __attribute__((ext_vector_type(4))) _Float16 f16x4;

@@ -1,12 +1,14 @@
 // distance.h — the exact fp32 distance tile, ||q||^2 + ||g||^2 - 2 q.g (evaluate.py:7-13,
-// reranking.py:36-41), shared by the distance kernels (distance.hip) and the fused search
-// (search.hip).  Device code and the host predicate that picks the mainloop; internal.
+// reranking.py:36-41), shared by the distance kernels (distance.hip) and the kernels that walk
+// the tile over a query band and a gallery range without storing it (search.hip, evalfeat.hip,
+// pairhist.hip, cluster.hip).  Device code, and the host side of the walk: the predicate that
+// picks the mainloop, the launch plan, the norms at the head of the workspace; internal.
 //
 // Bit-exact contract with oracle/reid_oracle.c: every dot product / squared norm is an
 // fmaf chain over k ascending.  The distance GEMM runs on v_mfma_f32_32x32x2_f32, whose
 // result is bit-for-bit that chain (one rounding per product, k-pairs in order).
 #pragma once
-#include "common.h"
+#include "backend.h"
 
 namespace reidmi {
 
@@ -179,9 +181,79 @@ __device__ __forceinline__ int64_t xcd_contiguous_wg() {
     return (xcd < r8 ? xcd * (q8 + 1) : r8 * (q8 + 1) + (xcd - r8) * q8) + (bid >> 3);
 }
 
-// Host: the operands allow dm_tile_pipe (the launchers of both users pick the mainloop by it).
+// ------------------------------------------------------------- the band-and-range walk
+// The kernels that select, count or join in the tile's epilogue instead of storing it
+// (search_f32_kernel, evf_count_kernel, ph_tile_kernel, dbs_tile_kernel) share one geometry: a
+// 256-thread workgroup owns one 128-row query band and one contiguous gallery range [c0, c1) of
+// range_len columns (whole tiles, unless a tool forces the ranges) and walks it in 128-column
+// tiles.  The grid is bands x S workgroups, at most the DM_SLOTS resident ones (dm_walk_plan).
+
+// Floats of LDS that hold the stages of either mainloop.
+constexpr int DM_SMEM = 2 * 2 * DM2_BK * DM2_LD;
+static_assert(DM_SMEM >= 2 * DM_BK * (DM_BM + DM_PAD), "dm_tile: both mainloops' stages fit");
+
+// One tile by the mainloop the launcher picked (dm2_ok), its stages carved out of smem[DM_SMEM].
+// Both mainloops end on a barrier: afterwards smem is free, for the next tile or the caller's use.
+template <bool PIPE>
+__device__ __forceinline__ void dm_tile(const DmThread& t, const float* q, const float* g, int64_t Q, int64_t glim,
+                                        int64_t D, int64_t ldq, int64_t ldg, int64_t bm, int64_t bn, float* smem,
+                                        f32x16 (&acc)[2][2]) {
+    if constexpr (PIPE)
+        dm_tile_pipe(t, q, g, Q, glim, D, ldq, ldg, bm, bn, (float(*)[DM2_BK][DM2_LD])smem,
+                     (float(*)[DM2_BK][DM2_LD])(smem + 2 * DM2_BK * DM2_LD), acc);
+    else
+        dm_tile_single(t, q, g, Q, glim, D, ldq, ldg, bm, bn, (float(*)[DM_BM + DM_PAD])smem,
+                       (float(*)[DM_BN + DM_PAD])(smem + DM_BK * (DM_BM + DM_PAD)), acc);
+}
+
+// This workgroup's place in the walk: band `band` (rows from bm) of `bands`, gallery range `split`
+// = columns [c0, c1).  Band fastest: the bands of one gallery range get consecutive numbers, so
+// they run side by side on one XCD and share the range's tiles in that L2.
+struct DmWalk {
+    int64_t bands, band, split, bm, c0, c1;
+};
+__device__ __forceinline__ DmWalk dm_walk(int64_t Q, int64_t G, int64_t range_len) {
+    const int64_t bands = (Q + DM_BM - 1) / DM_BM;
+    const int64_t wg = xcd_contiguous_wg();
+    const int64_t band = wg % bands, split = wg / bands, bm = band * DM_BM;
+    const int64_t c0 = split * range_len, c1 = c0 + range_len < G ? c0 + range_len : G;
+    return {bands, band, split, bm, c0, c1};
+}
+
+// Person and camera ids of the query and the gallery rows (evaluate.py:46-48).  Which of them may
+// be null is the entry point's contract.
+struct DmLabels {
+    const int64_t *qp, *qc, *gp, *gc;
+};
+
+// ---------------------------------------------------------------- the walk's host side
+// The operands allow dm_tile_pipe (every launcher picks the mainloop by it).
 inline bool dm2_ok(const float* q, int64_t ldq, const float* g, int64_t ldg, int64_t D) {
     return D % 4 == 0 && ldq % 4 == 0 && ldg % 4 == 0 && ((uintptr_t)q & 15) == 0 && ((uintptr_t)g & 15) == 0;
+}
+
+// The launch plan, a pure function of the shape: `tiles` gallery tiles cut into S ranges of
+// range_len columns (whole tiles) so that bands x S workgroups fill, and do not exceed, the
+// DM_SLOTS resident workgroups.  More bands than slots: one range per band.  No bands (Q == 0,
+// nothing is launched): one range.  The caller checks bands * S < 2^31 under its own name.
+constexpr int DM_SLOTS = 1024;  // 256 CUs x DM2_MINWG
+inline void dm_walk_plan(int64_t bands, int64_t tiles, int64_t* S, int64_t* range_len) {
+    int64_t s0 = bands > 0 ? DM_SLOTS / bands : 1;
+    s0 = s0 < 1 ? 1 : (s0 > tiles ? tiles : s0);
+    const int64_t per = (tiles + s0 - 1) / s0;
+    *S = (tiles + per - 1) / per;
+    *range_len = per * DM_BN;
+}
+
+// The head of every walk's workspace: the squared norms qq [Q] | gg [G], padded to 16 bytes.
+inline int64_t dm_norm_bytes(int64_t Q, int64_t G) { return ((Q + G) * 4 + 15) / 16 * 16; }
+inline int dm_norms(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G, int64_t ldg, int64_t D,
+                    float* qq, float* gg, hipStream_t s) {
+    rows_sqnorm_launch(q, Q, D, ldq, qq, s);
+    RM_LAUNCHED();
+    rows_sqnorm_launch(g, G, D, ldg, gg, s);
+    RM_LAUNCHED();
+    return OK;
 }
 
 }  // namespace reidmi

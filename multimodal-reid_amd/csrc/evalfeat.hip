@@ -16,10 +16,6 @@
 
 namespace reidmi {
 
-struct EvfLabels {
-    const int64_t *qp, *qc, *gp, *gc;
-};
-
 // ------------------------------------------------------------------------ matches
 // One workgroup per 128-query band and chunk of EVF_MCH gallery items: the band's labels sit in
 // LDS, every thread holds EVF_MU gallery labels and compares them with the 128 queries (LDS
@@ -27,7 +23,7 @@ struct EvfLabels {
 // atomics on the per-query counts do not contend.  The entry's distance is filled afterwards.
 constexpr int EVF_MU = 8, EVF_MCH = 256 * EVF_MU;
 
-__global__ __launch_bounds__(256) void evf_matches_kernel(EvfLabels lab, int64_t Q, int64_t Gb, int64_t bands,
+__global__ __launch_bounds__(256) void evf_matches_kernel(DmLabels lab, int64_t Q, int64_t Gb, int64_t bands,
                                                           int64_t base, int cap, float2* __restrict__ pos,
                                                           int32_t* __restrict__ pos_cnt,
                                                           int32_t* __restrict__ junk_cnt,
@@ -166,7 +162,7 @@ __global__ __launch_bounds__(256) void evf_sort_kernel(float2* pos, const int32_
 }
 
 // -------------------------------------------------------------------------- count
-// search_f32_kernel's structure: a workgroup owns one 128-row query band and one contiguous
+// distance.h's band-and-range walk: a workgroup owns one 128-row query band and one contiguous
 // gallery range [c0, c1) of the block and walks it in 128-column tiles with the distance kernels'
 // mainloops, so v below has the distance kernel's bits.  Row state in LDS: the squared norm, the
 // labels, the number of matches and the LAST match's key.  Epilogue per element: removed items
@@ -176,27 +172,20 @@ __global__ __launch_bounds__(256) void evf_sort_kernel(float2* pos, const int32_
 // Q * cap * 8 bytes) and add 1 to hist[i][b] (an L2 atomic; integer, so any order gives the same
 // sum).  LDS: 33 024 B of operand stages + 2.5 KB of row state + 2 KB of labels: four workgroups
 // per CU, as the search.
-constexpr int EVF_SLOTS = 1024;  // 256 CUs x DM2_MINWG
-constexpr int EVF_SMEM = 2 * 2 * DM2_BK * DM2_LD;  // floats
-static_assert(EVF_SMEM >= 2 * DM_BK * (DM_BM + DM_PAD), "evf_count: both mainloops' stages fit");
-
 template <bool PIPE>
 __global__ __launch_bounds__(256, DM2_MINWG) void evf_count_kernel(
     const float* __restrict__ q, const float* __restrict__ g, const float* __restrict__ qq,
-    const float* __restrict__ gg, int64_t Q, int64_t Gb, int64_t D, int64_t ldq, int64_t ldg, EvfLabels lab,
+    const float* __restrict__ gg, int64_t Q, int64_t Gb, int64_t D, int64_t ldq, int64_t ldg, DmLabels lab,
     int64_t range_len, int64_t base, int cap, const float2* __restrict__ pos, const int32_t* __restrict__ pos_cnt,
     int32_t* __restrict__ hist) {
-    __shared__ float smem[EVF_SMEM];
+    __shared__ float smem[DM_SMEM];
     __shared__ float s_qq[DM_BM], s_lv[DM_BM];
     __shared__ int s_li[DM_BM], s_m[DM_BM];
     __shared__ int64_t s_qp[DM_BM], s_qc[DM_BM];
     const DmThread t = dm_thread();
     const int tid = t.tid, lane = t.lane, wm = t.wm, wn = t.wn;
-    // band fastest: the bands of one gallery range run side by side on one XCD and share its tiles
-    const int64_t bands = (Q + DM_BM - 1) / DM_BM;
-    const int64_t wg = xcd_contiguous_wg();
-    const int64_t band = wg % bands, split = wg / bands, bm = band * DM_BM;
-    const int64_t c0 = split * range_len, c1 = c0 + range_len < Gb ? c0 + range_len : Gb;
+    const DmWalk w = dm_walk(Q, Gb, range_len);
+    const int64_t bm = w.bm, c0 = w.c0, c1 = w.c1;
     if (tid < DM_BM) {
         const bool in = bm + tid < Q;
         int m = in ? pos_cnt[bm + tid] : 0;
@@ -214,13 +203,7 @@ __global__ __launch_bounds__(256, DM2_MINWG) void evf_count_kernel(
     for (int64_t bn = c0; bn < c1; bn += DM_BN) {
         f32x16 acc[2][2];
         dm_acc_zero(acc);
-        if constexpr (PIPE)
-            dm_tile_pipe(t, q, g, Q, c1, D, ldq, ldg, bm, bn, (float(*)[DM2_BK][DM2_LD])smem,
-                         (float(*)[DM2_BK][DM2_LD])(smem + 2 * DM2_BK * DM2_LD), acc);
-        else
-            dm_tile_single(t, q, g, Q, c1, D, ldq, ldg, bm, bn, (float(*)[DM_BM + DM_PAD])smem,
-                           (float(*)[DM_BN + DM_PAD])(smem + DM_BK * (DM_BM + DM_PAD)), acc);
-        // both mainloops end on a barrier: the stages are free for the next tile
+        dm_tile<PIPE>(t, q, g, Q, c1, D, ldq, ldg, bm, bn, smem, acc);
 #pragma unroll
         for (int nt = 0; nt < 2; nt++) {
             const int64_t j = bn + dm_lane_col(wn, nt, lane);
@@ -255,11 +238,9 @@ __global__ __launch_bounds__(256, DM2_MINWG) void evf_count_kernel(
 }
 
 // ------------------------------------------------------------------------- launchers
-static int64_t evf_norm_bytes(int64_t Q, int64_t G) { return ((Q + G) * 4 + 15) / 16 * 16; }
-
 // The argument checks every entry point shares; all before any HIP call.
 static int evf_check(const char* who, int64_t Q, int64_t Gb, int64_t D, int64_t ldq, int64_t ldg, int64_t base,
-                     int cap, const EvfLabels& lab) {
+                     int cap, const DmLabels& lab) {
     const std::string w(who);
     RM_REQUIRE(Q >= 0 && Q < (1ll << 31) && Gb > 0 && D > 0, w + ": bad shape (need Q >= 0, G > 0, D > 0)");
     RM_REQUIRE(ldq >= D && ldg >= D, w + ": row pitches must be >= D");
@@ -271,7 +252,7 @@ static int evf_check(const char* who, int64_t Q, int64_t Gb, int64_t D, int64_t 
 }
 
 static int evf_matches_run(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t Gb, int64_t ldg,
-                           int64_t D, const EvfLabels& lab, const float* qq, const float* gg, int64_t base, int cap,
+                           int64_t D, const DmLabels& lab, const float* qq, const float* gg, int64_t base, int cap,
                            float2* pos, int32_t* pos_cnt, int32_t* junk_cnt, int32_t* overflow, hipStream_t s) {
     const int64_t bands = (Q + DM_BM - 1) / DM_BM, chunks = (Gb + EVF_MCH - 1) / EVF_MCH;
     RM_REQUIRE(bands * chunks < (1ll << 31), "evf_matches: too many (query band, gallery chunk) pairs for one launch");
@@ -280,12 +261,9 @@ static int evf_matches_run(const float* q, int64_t Q, int64_t ldq, const float* 
     RM_LAUNCHED();
     const int64_t blocks = (Q * cap + 255) / 256;
     const dim3 grid((unsigned)(blocks < 65536 ? blocks : 65536));
-    if (dm2_ok(q, ldq, g, ldg, D))
-        hipLaunchKernelGGL(evf_fill_kernel<true>, grid, dim3(256), 0, s, q, g, qq, gg, Q, Gb, D, ldq, ldg, base, cap,
-                           pos, (const int32_t*)pos_cnt);
-    else
-        hipLaunchKernelGGL(evf_fill_kernel<false>, grid, dim3(256), 0, s, q, g, qq, gg, Q, Gb, D, ldq, ldg, base, cap,
-                           pos, (const int32_t*)pos_cnt);
+    RM_BOOL_SWITCH(dm2_ok(q, ldq, g, ldg, D), VEC,
+                   hipLaunchKernelGGL(evf_fill_kernel<VEC>, grid, dim3(256), 0, s, q, g, qq, gg, Q, Gb, D, ldq, ldg,
+                                      base, cap, pos, (const int32_t*)pos_cnt));
     RM_LAUNCHED();
     return OK;
 }
@@ -296,32 +274,18 @@ static int evf_sort_run(float2* pos, const int32_t* pos_cnt, int64_t Q, int cap,
     return OK;
 }
 
-// The gallery ranges of the count: whole tiles, so that bands x S workgroups fill, and do not
-// exceed, the EVF_SLOTS resident workgroups (search.hip's sr_plan).
+// The gallery ranges of the count: distance.h's dm_walk_plan.
 static int evf_count_run(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t Gb, int64_t ldg, int64_t D,
-                         const EvfLabels& lab, const float* qq, const float* gg, int64_t base, int cap,
+                         const DmLabels& lab, const float* qq, const float* gg, int64_t base, int cap,
                          const float2* pos, const int32_t* pos_cnt, int32_t* hist, hipStream_t s) {
     const int64_t bands = (Q + DM_BM - 1) / DM_BM, tiles = (Gb + DM_BN - 1) / DM_BN;
-    int64_t s0 = EVF_SLOTS / bands;
-    s0 = s0 < 1 ? 1 : (s0 > tiles ? tiles : s0);
-    const int64_t per = (tiles + s0 - 1) / s0, S = (tiles + per - 1) / per, range_len = per * DM_BN;
+    int64_t S, range_len;
+    dm_walk_plan(bands, tiles, &S, &range_len);
     RM_REQUIRE(bands * S < (1ll << 31), "evf_count: too many query bands for one launch");
     const dim3 grid((unsigned)(bands * S));
-    if (dm2_ok(q, ldq, g, ldg, D))
-        hipLaunchKernelGGL(evf_count_kernel<true>, grid, dim3(256), 0, s, q, g, qq, gg, Q, Gb, D, ldq, ldg, lab,
-                           range_len, base, cap, pos, pos_cnt, hist);
-    else
-        hipLaunchKernelGGL(evf_count_kernel<false>, grid, dim3(256), 0, s, q, g, qq, gg, Q, Gb, D, ldq, ldg, lab,
-                           range_len, base, cap, pos, pos_cnt, hist);
-    RM_LAUNCHED();
-    return OK;
-}
-
-static int evf_norms(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G, int64_t ldg, int64_t D,
-                     float* qq, float* gg, hipStream_t s) {
-    rows_sqnorm_launch(q, Q, D, ldq, qq, s);
-    RM_LAUNCHED();
-    rows_sqnorm_launch(g, G, D, ldg, gg, s);
+    RM_BOOL_SWITCH(dm2_ok(q, ldq, g, ldg, D), PIPE,
+                   hipLaunchKernelGGL(evf_count_kernel<PIPE>, grid, dim3(256), 0, s, q, g, qq, gg, Q, Gb, D, ldq, ldg,
+                                      lab, range_len, base, cap, pos, pos_cnt, hist));
     RM_LAUNCHED();
     return OK;
 }
@@ -332,7 +296,7 @@ struct EvfWs {
 };
 static bool evf_ws(int64_t Q, int64_t G, int64_t D, int cap, EvfWs* w) {
     if (Q < 0 || Q >= (1ll << 31) || G <= 0 || G >= (1ll << 31) || D <= 0 || cap < 1) return false;
-    w->pos_off = evf_norm_bytes(Q, G);
+    w->pos_off = dm_norm_bytes(Q, G);
     w->zero_off = w->pos_off + Q * cap * 8;
     w->zero_bytes = (Q * 8 + Q * ((int64_t)cap + 1) * 4 + 15) / 16 * 16;
     w->bytes = w->zero_off + w->zero_bytes;
@@ -343,23 +307,17 @@ static bool evf_ws(int64_t Q, int64_t G, int64_t D, int cap, EvfWs* w) {
 
 using namespace reidmi;
 
-#define EVF_TRY(expr)              \
-    do {                           \
-        const int rc_ = (expr);    \
-        if (rc_ != OK) return rc_; \
-    } while (0)
-
 REIDMI_API int64_t reidmi_evf_workspace_bytes(int64_t Q, int64_t Gb) {
-    return Q >= 0 && Gb > 0 ? evf_norm_bytes(Q, Gb) : -1;
+    return Q >= 0 && Gb > 0 ? dm_norm_bytes(Q, Gb) : -1;
 }
 
 REIDMI_API int reidmi_evf_matches(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t Gb, int64_t ldg,
                                   int64_t D, const int64_t* q_pids, const int64_t* q_cams, const int64_t* g_pids,
                                   const int64_t* g_cams, int64_t base, int cap, void* pos, int32_t* pos_cnt,
                                   int32_t* junk_cnt, int32_t* overflow, void* ws, int64_t ws_bytes, void* stream) {
-    const EvfLabels lab{q_pids, q_cams, g_pids, g_cams};
-    EVF_TRY(evf_check("evf_matches", Q, Gb, D, ldq, ldg, base, cap, lab));
-    RM_REQUIRE(ws != nullptr && ((uintptr_t)ws & 15) == 0 && ws_bytes >= evf_norm_bytes(Q, Gb),
+    const DmLabels lab{q_pids, q_cams, g_pids, g_cams};
+    RM_TRY(evf_check("evf_matches", Q, Gb, D, ldq, ldg, base, cap, lab));
+    RM_REQUIRE(ws != nullptr && ((uintptr_t)ws & 15) == 0 && ws_bytes >= dm_norm_bytes(Q, Gb),
                "evf_matches: workspace (reidmi_evf_workspace_bytes, 16-byte aligned) required");
     RM_REQUIRE(pos != nullptr && ((uintptr_t)pos & 7) == 0 && pos_cnt != nullptr && junk_cnt != nullptr &&
                    overflow != nullptr,
@@ -369,7 +327,7 @@ REIDMI_API int reidmi_evf_matches(const float* q, int64_t Q, int64_t ldq, const 
     hipStream_t s = (hipStream_t)stream;
     float* qq = (float*)ws;
     float* gg = qq + Q;
-    EVF_TRY(evf_norms(q, Q, ldq, g, Gb, ldg, D, qq, gg, s));
+    RM_TRY(dm_norms(q, Q, ldq, g, Gb, ldg, D, qq, gg, s));
     return evf_matches_run(q, Q, ldq, g, Gb, ldg, D, lab, qq, gg, base, cap, (float2*)pos, pos_cnt, junk_cnt, overflow,
                            s);
 }
@@ -401,9 +359,9 @@ REIDMI_API int reidmi_evf_count(const float* q, int64_t Q, int64_t ldq, const fl
                                 int64_t D, const int64_t* q_pids, const int64_t* q_cams, const int64_t* g_pids,
                                 const int64_t* g_cams, int64_t base, int cap, const void* pos, const int32_t* pos_cnt,
                                 int32_t* hist, void* ws, int64_t ws_bytes, void* stream) {
-    const EvfLabels lab{q_pids, q_cams, g_pids, g_cams};
-    EVF_TRY(evf_check("evf_count", Q, Gb, D, ldq, ldg, base, cap, lab));
-    RM_REQUIRE(ws != nullptr && ((uintptr_t)ws & 15) == 0 && ws_bytes >= evf_norm_bytes(Q, Gb),
+    const DmLabels lab{q_pids, q_cams, g_pids, g_cams};
+    RM_TRY(evf_check("evf_count", Q, Gb, D, ldq, ldg, base, cap, lab));
+    RM_REQUIRE(ws != nullptr && ((uintptr_t)ws & 15) == 0 && ws_bytes >= dm_norm_bytes(Q, Gb),
                "evf_count: workspace (reidmi_evf_workspace_bytes, 16-byte aligned) required");
     RM_REQUIRE(pos != nullptr && ((uintptr_t)pos & 7) == 0 && pos_cnt != nullptr && hist != nullptr,
                "evf_count: pos (8-byte aligned), pos_cnt and hist required");
@@ -412,7 +370,7 @@ REIDMI_API int reidmi_evf_count(const float* q, int64_t Q, int64_t ldq, const fl
     hipStream_t s = (hipStream_t)stream;
     float* qq = (float*)ws;
     float* gg = qq + Q;
-    EVF_TRY(evf_norms(q, Q, ldq, g, Gb, ldg, D, qq, gg, s));
+    RM_TRY(dm_norms(q, Q, ldq, g, Gb, ldg, D, qq, gg, s));
     return evf_count_run(q, Q, ldq, g, Gb, ldg, D, lab, qq, gg, base, cap, (const float2*)pos, pos_cnt, hist, s);
 }
 
@@ -433,8 +391,8 @@ REIDMI_API int reidmi_eval_feat_f32(const float* q, int64_t Q, int64_t ldq, cons
                                     const int64_t* g_cams, int cap, int32_t* valid, int64_t* first, int64_t* last,
                                     int32_t* npos, double* ap, int64_t* nkept, int32_t* overflow, void* ws,
                                     int64_t ws_bytes, void* stream) {
-    const EvfLabels lab{q_pids, q_cams, g_pids, g_cams};
-    EVF_TRY(evf_check("eval_feat", Q, G, D, ldq, ldg, 0, cap, lab));
+    const DmLabels lab{q_pids, q_cams, g_pids, g_cams};
+    RM_TRY(evf_check("eval_feat", Q, G, D, ldq, ldg, 0, cap, lab));
     EvfWs w;
     RM_REQUIRE(evf_ws(Q, G, D, cap, &w) && ws != nullptr && ((uintptr_t)ws & 15) == 0 && ws_bytes >= w.bytes,
                "eval_feat: workspace (reidmi_eval_feat_workspace_bytes, 16-byte aligned) required");
@@ -451,9 +409,9 @@ REIDMI_API int reidmi_eval_feat_f32(const float* q, int64_t Q, int64_t ldq, cons
     int32_t* hist = junk_cnt + Q;
     RM_CHECK_HIP(hipMemsetAsync(pos_cnt, 0, (size_t)w.zero_bytes, s));
     RM_CHECK_HIP(hipMemsetAsync(overflow, 0, sizeof(int32_t), s));
-    EVF_TRY(evf_norms(q, Q, ldq, g, G, ldg, D, qq, gg, s));
-    EVF_TRY(evf_matches_run(q, Q, ldq, g, G, ldg, D, lab, qq, gg, 0, cap, pos, pos_cnt, junk_cnt, overflow, s));
-    EVF_TRY(evf_sort_run(pos, pos_cnt, Q, cap, s));
-    EVF_TRY(evf_count_run(q, Q, ldq, g, G, ldg, D, lab, qq, gg, 0, cap, pos, pos_cnt, hist, s));
+    RM_TRY(dm_norms(q, Q, ldq, g, G, ldg, D, qq, gg, s));
+    RM_TRY(evf_matches_run(q, Q, ldq, g, G, ldg, D, lab, qq, gg, 0, cap, pos, pos_cnt, junk_cnt, overflow, s));
+    RM_TRY(evf_sort_run(pos, pos_cnt, Q, cap, s));
+    RM_TRY(evf_count_run(q, Q, ldq, g, G, ldg, D, lab, qq, gg, 0, cap, pos, pos_cnt, hist, s));
     return evf_finish_launch(pos_cnt, hist, junk_cnt, Q, cap, G, overflow, valid, first, last, npos, ap, nkept, s);
 }

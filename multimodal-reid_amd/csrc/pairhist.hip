@@ -3,8 +3,8 @@
 //
 // Per labelled (query, gallery item) pair: the bin of its distance under the caller's edges,
 // counted apart for genuine and impostor pairs, and per query the nearest genuine and the nearest
-// impostor item.  evf_count_kernel's structure (evalfeat.hip): the distance kernels' mainloop
-// (distance.h), so d(i, j) has reidmi_distmat_f32's bits, with another epilogue; no tile is stored.
+// impostor item.  distance.h's band-and-range walk: the distance kernels' mainloop, so d(i, j)
+// has reidmi_distmat_f32's bits, with an epilogue of its own; no tile is stored.
 //
 // Why the result does not depend on scheduling.  The histograms are integer sums: any order of the
 // adds, in LDS or in global memory, gives the same counts.  A nearest item is the minimum of a
@@ -16,9 +16,6 @@
 
 namespace reidmi {
 
-constexpr int PH_SLOTS = 1024;                     // 256 CUs x DM2_MINWG
-constexpr int PH_SMEM = 2 * 2 * DM2_BK * DM2_LD;   // floats: both mainloops' stages
-static_assert(PH_SMEM >= 2 * DM_BK * (DM_BM + DM_PAD), "ph_tile: both mainloops' stages fit");
 constexpr int PH_MAX_EDGES = 255, PH_BINS = PH_MAX_EDGES + 1;
 // An LDS bin is 32 bits wide and a tile adds at most DM_BM * DM_BN = 2^14 to one: the bins are
 // flushed to the 64-bit global counters at the range's end and after every PH_FLUSH_TILES tiles,
@@ -29,10 +26,6 @@ constexpr unsigned long long PH_NOKEY = ~0ull;  // no item: above every key (an 
 // The edges travel by value in the kernel arguments (no copy, no synchronisation): e[n..] = +inf.
 struct PhEdges {
     float e[PH_BINS];
-};
-
-struct PhLabels {
-    const int64_t *qp, *qc, *gp, *gc;  // qc, gc: both or neither
 };
 
 // fp32 bits as an unsigned integer in the order of fp32 `<`; -0.0 is made +0.0 first, so the two
@@ -58,11 +51,11 @@ __device__ __forceinline__ float ph_unordered(unsigned o) {
 template <bool PIPE>
 __global__ __launch_bounds__(256, DM2_MINWG) void ph_tile_kernel(
     const float* __restrict__ q, const float* __restrict__ g, const float* __restrict__ qq,
-    const float* __restrict__ gg, int64_t Q, int64_t Gb, int64_t D, int64_t ldq, int64_t ldg, PhLabels lab,
+    const float* __restrict__ gg, int64_t Q, int64_t Gb, int64_t D, int64_t ldq, int64_t ldg, DmLabels lab,
     PhEdges edges, int64_t range_len, int64_t index_base, int64_t self_base,
     unsigned long long* __restrict__ hist_pos, unsigned long long* __restrict__ hist_neg,
     unsigned long long* __restrict__ key_pos, unsigned long long* __restrict__ key_neg) {
-    __shared__ float smem[PH_SMEM];
+    __shared__ float smem[DM_SMEM];
     __shared__ float s_edges[PH_BINS];
     __shared__ unsigned s_hist[2][PH_BINS];         // [0] impostor, [1] genuine
     __shared__ unsigned long long s_key[2][DM_BM];  // likewise
@@ -70,12 +63,9 @@ __global__ __launch_bounds__(256, DM2_MINWG) void ph_tile_kernel(
     __shared__ int64_t s_qp[DM_BM], s_qc[DM_BM];
     const DmThread t = dm_thread();
     const int tid = t.tid, lane = t.lane, wm = t.wm, wn = t.wn;
-    const bool cams = lab.qc != nullptr;
-    // band fastest: the bands of one gallery range run side by side on one XCD and share its tiles
-    const int64_t bands = (Q + DM_BM - 1) / DM_BM;
-    const int64_t wg = xcd_contiguous_wg();
-    const int64_t band = wg % bands, split = wg / bands, bm = band * DM_BM;
-    const int64_t c0 = split * range_len, c1 = c0 + range_len < Gb ? c0 + range_len : Gb;
+    const bool cams = lab.qc != nullptr;  // qc, gc: both or neither
+    const DmWalk w = dm_walk(Q, Gb, range_len);
+    const int64_t bm = w.bm, c0 = w.c0, c1 = w.c1;
     const int nq = Q - bm < DM_BM ? (int)(Q - bm) : DM_BM;
     s_edges[tid] = edges.e[tid];
     s_hist[0][tid] = 0;
@@ -101,13 +91,7 @@ __global__ __launch_bounds__(256, DM2_MINWG) void ph_tile_kernel(
     for (int64_t bn = c0; bn < c1; bn += DM_BN) {
         f32x16 acc[2][2];
         dm_acc_zero(acc);
-        if constexpr (PIPE)
-            dm_tile_pipe(t, q, g, Q, c1, D, ldq, ldg, bm, bn, (float(*)[DM2_BK][DM2_LD])smem,
-                         (float(*)[DM2_BK][DM2_LD])(smem + 2 * DM2_BK * DM2_LD), acc);
-        else
-            dm_tile_single(t, q, g, Q, c1, D, ldq, ldg, bm, bn, (float(*)[DM_BM + DM_PAD])smem,
-                           (float(*)[DM_BN + DM_PAD])(smem + DM_BK * (DM_BM + DM_PAD)), acc);
-        // both mainloops end on a barrier: the stages are free for the next tile
+        dm_tile<PIPE>(t, q, g, Q, c1, D, ldq, ldg, bm, bn, smem, acc);
         // everything per element below is 32-bit: row il of the band, the column's index as the result
         // carries it, and the band row a column forms a self pair with (-1: none)
         int64_t gpj[2], gcj[2];
@@ -185,9 +169,8 @@ __global__ __launch_bounds__(256) void ph_finish_kernel(const unsigned long long
 }
 
 // workspace: norms | key_pos [Q] | key_neg [Q]
-static int64_t ph_norm_bytes(int64_t Q, int64_t G) { return ((Q + G) * 4 + 15) / 16 * 16; }
 static bool ph_shape_ok(int64_t Q, int64_t G) { return Q >= 0 && Q < (1ll << 31) && G >= 1 && G < (1ll << 31); }
-static int64_t ph_ws_bytes(int64_t Q, int64_t G) { return ph_norm_bytes(Q, G) + 2 * Q * 8; }
+static int64_t ph_ws_bytes(int64_t Q, int64_t G) { return dm_norm_bytes(Q, G) + 2 * Q * 8; }
 
 }  // namespace reidmi
 
@@ -226,33 +209,25 @@ REIDMI_API int reidmi_pair_stats_f32(const float* q, int64_t Q, int64_t ldq, con
                "pair_stats: workspace (reidmi_pair_stats_workspace_bytes, 16-byte aligned) required");
     RM_REQUIRE(q != nullptr && g != nullptr, "pair_stats: features required");
     if (Q == 0) return OK;
-    // the gallery ranges: whole tiles, so that bands x S workgroups fill, and do not exceed, the
-    // PH_SLOTS resident workgroups (evalfeat.hip's evf_count_run)
+    // the gallery ranges: distance.h's dm_walk_plan
     const int64_t bands = (Q + DM_BM - 1) / DM_BM, tiles = (G + DM_BN - 1) / DM_BN;
-    int64_t s0 = PH_SLOTS / bands;
-    s0 = s0 < 1 ? 1 : (s0 > tiles ? tiles : s0);
-    const int64_t per = (tiles + s0 - 1) / s0, S = (tiles + per - 1) / per, range_len = per * DM_BN;
+    int64_t S, range_len;
+    dm_walk_plan(bands, tiles, &S, &range_len);
     RM_REQUIRE(bands * S < (1ll << 31), "pair_stats: too many query bands for one launch");
     hipStream_t s = (hipStream_t)stream;
     float* qq = (float*)ws;
     float* gg = qq + Q;
-    unsigned long long* key_pos = (unsigned long long*)((char*)ws + ph_norm_bytes(Q, G));
+    unsigned long long* key_pos = (unsigned long long*)((char*)ws + dm_norm_bytes(Q, G));
     unsigned long long* key_neg = key_pos + Q;
     RM_CHECK_HIP(hipMemsetAsync(key_pos, 0xff, (size_t)(2 * Q * 8), s));
-    rows_sqnorm_launch(q, Q, D, ldq, qq, s);
-    RM_LAUNCHED();
-    rows_sqnorm_launch(g, G, D, ldg, gg, s);
-    RM_LAUNCHED();
-    const PhLabels lab{q_pids, q_cams, g_pids, g_cams};
+    RM_TRY(dm_norms(q, Q, ldq, g, G, ldg, D, qq, gg, s));
+    const DmLabels lab{q_pids, q_cams, g_pids, g_cams};
     const dim3 grid((unsigned)(bands * S));
-    if (dm2_ok(q, ldq, g, ldg, D))
-        hipLaunchKernelGGL(ph_tile_kernel<true>, grid, dim3(256), 0, s, q, g, (const float*)qq, (const float*)gg, Q, G,
-                           D, ldq, ldg, lab, pe, range_len, index_base, self_base, (unsigned long long*)hist_pos,
-                           (unsigned long long*)hist_neg, key_pos, key_neg);
-    else
-        hipLaunchKernelGGL(ph_tile_kernel<false>, grid, dim3(256), 0, s, q, g, (const float*)qq, (const float*)gg, Q, G,
-                           D, ldq, ldg, lab, pe, range_len, index_base, self_base, (unsigned long long*)hist_pos,
-                           (unsigned long long*)hist_neg, key_pos, key_neg);
+    RM_BOOL_SWITCH(dm2_ok(q, ldq, g, ldg, D), PIPE,
+                   hipLaunchKernelGGL(ph_tile_kernel<PIPE>, grid, dim3(256), 0, s, q, g, (const float*)qq,
+                                      (const float*)gg, Q, G, D, ldq, ldg, lab, pe, range_len, index_base, self_base,
+                                      (unsigned long long*)hist_pos, (unsigned long long*)hist_neg, key_pos,
+                                      key_neg));
     RM_LAUNCHED();
     hipLaunchKernelGGL(ph_finish_kernel, dim3((unsigned)((Q + 255) / 256)), dim3(256), 0, s,
                        (const unsigned long long*)key_pos, (const unsigned long long*)key_neg, Q, near_pos_dist,

@@ -70,11 +70,11 @@ int topk_launch(const float* x, int64_t rows, int64_t cols, int64_t ldx, const f
 
 // ------------------------------------------------------------- fused top-k search
 // reidmi_search_f32: the k nearest gallery rows of every query row without the Q x G matrix.
-// A workgroup owns one 128-row query band and one contiguous gallery range [c0, c1); it walks
-// the range in 128-column tiles with the distance kernels' mainloops (PIPE: a copy of
-// dm_tile_pipe, else dm_tile_single, whose K-step is the distance kernels' dm_kstep) and their
-// v = dm_value, so v below has the distance kernel's bits, and selects in the epilogue instead
-// of storing:
+// distance.h's band-and-range walk: a workgroup owns one 128-row query band and one contiguous
+// gallery range [c0, c1) and walks it in 128-column tiles with the distance kernels' mainloops
+// (PIPE: a copy of dm_tile_pipe, else dm_tile_single, whose K-step is the distance kernels'
+// dm_kstep) and their v = dm_value, so v below has the distance kernel's bits, and selects in
+// the epilogue instead of storing:
 //   * (v, j) is kept when j passes the label predicate and key_less(v, j, thr[row]); thr[row]
 //     is the row's bound (none: +inf) until K candidates were seen, then its current K-th key, in
 //     LDS, and only falls; s_own says which of the two it is (a bounded row that collects K
@@ -91,13 +91,9 @@ int topk_launch(const float* x, int64_t rows, int64_t cols, int64_t ldx, const f
 // of a row.  LDS: 33 024 B of operand stages (reused as the compaction scratch, 4 waves x cap
 // x 8 B) + 2.5 KB of row state (+ 2 KB of query labels): four workgroups per CU, as the distance
 // kernel.
-constexpr int SR_K_MAX = 128, SR_CAP_MAX = 512 /* 4 waves x 512 x 8 B of scratch fit the stages */, SR_SLOTS = 1024 /* 256 CUs x DM2_MINWG */;
-constexpr int SR_SMEM = 2 * 2 * DM2_BK * DM2_LD;  // floats
-static_assert(SR_SMEM >= 2 * DM_BK * (DM_BM + DM_PAD) && SR_SMEM >= 4 * SR_CAP_MAX * 2, "search: LDS reuse");
+constexpr int SR_K_MAX = 128, SR_CAP_MAX = 512 /* 4 waves x 512 x 8 B of scratch fit the stages */;
+static_assert(DM_SMEM >= 4 * SR_CAP_MAX * 2, "search: the compaction scratch fits the stages");
 
-struct SrLabels {
-    const int64_t *qp, *qc, *gp, *gc;
-};
 // reidmi_search_bounded_f32's per-query bound: (dist[i * ld], idx[i * ld]), the index in the space
 // where this gallery's item j is base + j.  dist == nullptr: no bound; idx == nullptr: the
 // inclusive radius form.  Read once, in the kernel's prologue.
@@ -145,21 +141,17 @@ __device__ __forceinline__ void sr_compact_row(float2* __restrict__ list, uint64
 template <bool PIPE, bool LABELS>
 __global__ __launch_bounds__(256, DM2_MINWG) void search_f32_kernel(
     const float* __restrict__ q, const float* __restrict__ g, const float* __restrict__ qq,
-    const float* __restrict__ gg, int64_t Q, int64_t G, int64_t D, int64_t ldq, int64_t ldg, int K, SrLabels lab,
+    const float* __restrict__ gg, int64_t Q, int64_t G, int64_t D, int64_t ldq, int64_t ldg, int K, DmLabels lab,
     SrBound bnd, int64_t range_len, int cap, float2* __restrict__ lists, int32_t* __restrict__ stats) {
-    __shared__ float smem[SR_SMEM];
+    __shared__ float smem[DM_SMEM];
     __shared__ float s_tv[DM_BM], s_qq[DM_BM];
     __shared__ int s_ti[DM_BM], s_cnt[DM_BM], s_own[DM_BM];
     __shared__ int64_t s_qp[LABELS ? DM_BM : 1], s_qc[LABELS ? DM_BM : 1];
     const DmThread t = dm_thread();
     const int tid = t.tid, lane = t.lane, wid = t.wid, wm = t.wm, wn = t.wn;
-    // band fastest: the bands of one gallery range run side by side on one XCD and share its
-    // tiles in that L2
-    const int64_t bands = (Q + DM_BM - 1) / DM_BM;
-    const int64_t wg = xcd_contiguous_wg();
-    const int64_t band = wg % bands, split = wg / bands, bm = band * DM_BM;
-    const int64_t c0 = split * range_len, c1 = c0 + range_len < G ? c0 + range_len : G;
-    float2* const mylists = lists + (split * bands + band) * DM_BM * (int64_t)cap;
+    const DmWalk w = dm_walk(Q, G, range_len);
+    const int64_t bm = w.bm, c0 = w.c0, c1 = w.c1;
+    float2* const mylists = lists + (w.split * w.bands + w.band) * DM_BM * (int64_t)cap;
     if (tid < DM_BM) {
         const bool in = bm + tid < Q;
         // The row's running threshold starts at its bound (none: (+inf, every index)), so the
@@ -256,8 +248,7 @@ __global__ __launch_bounds__(256, DM2_MINWG) void search_f32_kernel(
                     __syncthreads();
                 }
             } else {
-                dm_tile_single(t, q, g, Q, c1, D, ldq, ldg, bm, bn, (float(*)[DM_BM + DM_PAD])smem,
-                               (float(*)[DM_BN + DM_PAD])(smem + DM_BK * (DM_BM + DM_PAD)), acc);
+                dm_tile<false>(t, q, g, Q, c1, D, ldq, ldg, bm, bn, smem, acc);
             }
             // epilogue: the distance kernels' v, filtered against the row's threshold.  il and j are
             // dm_lane_row / dm_lane_col written out: through the functions the kernel spills 8 B more per lane
@@ -368,9 +359,8 @@ int search_merge_launch(const int32_t* in_idx, const float* in_dist, int S, int6
     return OK;
 }
 
-// The launcher's choices, pure functions of the arguments: S gallery ranges of range_len columns
-// (whole tiles) so that bands x S workgroups fill, and do not exceed, the SR_SLOTS resident
-// workgroups; a forced S (tools) cuts G into ceil(G / S) columns per range, tile-aligned or not.
+// The launcher's choices, pure functions of the arguments: distance.h's dm_walk_plan; a forced S
+// (tools) cuts G into ceil(G / S) columns per range, tile-aligned or not.
 struct SrPlan {
     int64_t bands, S, range_len;
     int cap;
@@ -380,11 +370,7 @@ static bool sr_plan(int64_t Q, int64_t G, int k, int splits, int cap, SrPlan* p)
     p->bands = (Q + DM_BM - 1) / DM_BM;
     const int64_t tiles = (G + DM_BN - 1) / DM_BN;
     if (splits == 0) {
-        int64_t s0 = p->bands > 0 ? SR_SLOTS / p->bands : 1;
-        s0 = s0 < 1 ? 1 : (s0 > tiles ? tiles : s0);
-        const int64_t per = (tiles + s0 - 1) / s0;
-        p->S = (tiles + per - 1) / per;
-        p->range_len = per * DM_BN;
+        dm_walk_plan(p->bands, tiles, &p->S, &p->range_len);
     } else {
         if (splits < 1 || splits > 4096 || splits > G) return false;
         p->S = splits;
@@ -395,9 +381,9 @@ static bool sr_plan(int64_t Q, int64_t G, int k, int splits, int cap, SrPlan* p)
     p->cap = cap;
     return p->S * k < (1ll << 31) && p->bands * p->S < (1ll << 31);
 }
-static int64_t sr_lists_off(int64_t Q, int64_t G) { return ((Q + G) * 4 + 15) / 16 * 16; }
+// workspace: norms | the lists
 static int64_t sr_ws_bytes(int64_t Q, int64_t G, const SrPlan& p) {
-    return sr_lists_off(Q, G) + p.bands * p.S * DM_BM * p.cap * 8;
+    return dm_norm_bytes(Q, G) + p.bands * p.S * DM_BM * p.cap * 8;
 }
 
 int search_impl(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G, int64_t ldg, int64_t D, int k,
@@ -425,26 +411,16 @@ int search_impl(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t 
     hipStream_t s = (hipStream_t)stream;
     float* qq = (float*)ws;
     float* gg = qq + Q;
-    float2* lists = (float2*)((char*)ws + sr_lists_off(Q, G));
-    rows_sqnorm_launch(q, Q, D, ldq, qq, s);
-    RM_LAUNCHED();
-    rows_sqnorm_launch(g, G, D, ldg, gg, s);
-    RM_LAUNCHED();
-    const SrLabels lab{q_pids, q_cams, g_pids, g_cams};
+    float2* lists = (float2*)((char*)ws + dm_norm_bytes(Q, G));
+    RM_TRY(dm_norms(q, Q, ldq, g, G, ldg, D, qq, gg, s));
+    const DmLabels lab{q_pids, q_cams, g_pids, g_cams};
     const SrBound bnd{bound_dist, bound_idx, ldb, index_base};
     const dim3 grid((unsigned)(p.bands * p.S));
-    const bool pipe = dm2_ok(q, ldq, g, ldg, D);
-#define SR_LAUNCH(PIPE, LAB)                                                                                      \
-    hipLaunchKernelGGL((search_f32_kernel<PIPE, LAB>), grid, dim3(256), 0, s, q, g, qq, gg, Q, G, D, ldq, ldg, k, \
-                       lab, bnd, p.range_len, p.cap, lists, stats)
-    if (pipe) {
-        if (nlab) SR_LAUNCH(true, true);
-        else SR_LAUNCH(true, false);
-    } else {
-        if (nlab) SR_LAUNCH(false, true);
-        else SR_LAUNCH(false, false);
-    }
-#undef SR_LAUNCH
+    RM_BOOL_SWITCH(dm2_ok(q, ldq, g, ldg, D), PIPE,
+                   RM_BOOL_SWITCH(nlab != 0, LABELS,
+                                  hipLaunchKernelGGL((search_f32_kernel<PIPE, LABELS>), grid, dim3(256), 0, s, q, g,
+                                                     qq, gg, Q, G, D, ldq, ldg, k, lab, bnd, p.range_len, p.cap,
+                                                     lists, stats)));
     RM_LAUNCHED();
     hipLaunchKernelGGL(search_merge_kernel, dim3((unsigned)Q), dim3(256), 0, s, (const float2*)lists, p.bands,
                        (int)p.S, p.cap, k, out_idx, out_dist, ldo);

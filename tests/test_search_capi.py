@@ -35,6 +35,29 @@ def test_search_workspace_has_no_q_by_g_term():
         assert L.reidmi_search_workspace_bytes(*bad) < 0, bad
 
 
+# (Q, G, k) -> bytes, recorded from the library before the launch plan moved into distance.h
+# (dm_walk_plan).  The value is the norms plus bands * S * 128 * cap * 8, so it pins S: no bands,
+# one tile, ranges clamped by the tile count, both default capacities, more tiles than the 1024
+# slots, more bands than slots.
+WORKSPACE_BYTES = {
+    (0, 100, 5): 400,
+    (1, 1, 1): 262160,
+    (1, 129, 10): 524816,
+    (129, 300, 64): 1574592,
+    (129, 129, 128): 1573904,
+    (1000, 20000, 65): 248596512,
+    (3368, 15913, 50): 226569552,
+    (128, 131073, 10): 135004688,
+    (200000, 5000, 10): 410551072,
+}
+
+
+def test_search_workspace_bytes_recorded_plan():
+    L = _lib()
+    got = {s: L.reidmi_search_workspace_bytes(s[0], s[1], D, s[2]) for s in WORKSPACE_BYTES}
+    assert got == WORKSPACE_BYTES
+
+
 @pytest.mark.parametrize("k,G_,what", [(0, G, b"1 <= k <= G"), (41, 40, b"1 <= k <= G"), (-3, G, b"1 <= k <= G")])
 def test_search_refuses_k_out_of_range(k, G_, what):
     L = _lib()
