@@ -35,7 +35,9 @@ const char* reidmi_last_error(void);
  * 9: reidmi_search_bounded_f32 added.
  * 10: reidmi_dbscan_f32 added.
  * 11: reidmi_rr_jaccard_self_rows and reidmi_dbscan_jaccard added.
- * 12: reidmi_pair_stats_f32 added. */
+ * 12: reidmi_pair_stats_f32 added.
+ * 13: reidmi_search_prefiltered_f32, reidmi_search_prefilter_applies and
+ *     reidmi_search_prefiltered_workspace_bytes added. */
 int reidmi_abi_version(void);
 
 /* ------------------------------------------------------------ retrieval back end */
@@ -130,6 +132,51 @@ int reidmi_search_bounded_f32(const float* q, int64_t Q, int64_t ldq, const floa
                               const int64_t* g_cams, const float* bound_dist, const int32_t* bound_idx, int64_t ldb,
                               int64_t index_base, int32_t* out_idx, float* out_dist, int64_t ldo, void* ws,
                               int64_t ws_bytes, void* stream);
+
+/* reidmi_search_bounded_f32 with an fp16 pre-filter: the same rank lists, bit for bit, for most rows
+ * at a fraction of the exact search's fp32 MFMA work.  An fp16 MFMA product bounds every exact
+ * distance from above (hi) and, through the row's bound width w, from below (hi - w); a sample of
+ * the gallery (every sample_stride-th item) gives each row a threshold T = min(the k-th smallest hi
+ * among the sample items the label rule leaves, the row's bound distance); a second fp16 product
+ * over the whole gallery keeps, in its epilogue, only the pairs with hi - w <= T (at most 4096 per
+ * row); their exact distances (the chain of reidmi_distmat_f32) are computed, the admissibility of
+ * reidmi_search_bounded_f32 is applied to the exact key and the k smallest by (d, j) are written.
+ * Every argument up to ldo is reidmi_search_bounded_f32's, with its labels, bound (bound_dist ==
+ * NULL: the unbounded search), index_base, padding (-1 / +inf), tie order and refusals.
+ * need: device int32 [Q], written for every row.  need[i] == 0: out_idx / out_dist row i hold, bit
+ * for bit, what reidmi_search_bounded_f32 writes on the same inputs.  need[i] == 1: the row has no
+ * output and the caller runs the exact search for it (more than 4096 survivors: distances too
+ * concentrated for the bound to separate; a non-finite bound; or, for every row at once, a feature
+ * beyond +-2^15 or not finite, which fp16 cannot hold).
+ * sample_stride: S >= 2, or 0 for the default (16).  The sample is floor(G / S) items rounded down to
+ * whole 256-column tiles.  reidmi_search_prefilter_applies (a pure host function) returns 1 when the
+ * call can run: D padded to 64 is >= 128, and the sample spans at least one 256-column tile and at
+ * least 4 k items (and the shapes, k and sample_stride are themselves valid); otherwise 0, and
+ * reidmi_search_prefiltered_f32 refuses with REIDMI_EINVAL.
+ * stats: device int32 [4], nullable, written by the call: the rows marked in need; the largest
+ * survivor count of any row (4097: a row marked by its sample bounds); the candidates whose exact
+ * distance was computed, summed over the rows (saturating at 2^31 - 1); 1 if the fp16 range check
+ * failed (then every row is marked).
+ * ws: reidmi_search_prefiltered_workspace_bytes(Q, G, D, k, sample_stride) bytes (negative: bad
+ * shapes or the pre-filter does not apply), 16-byte aligned, holding in 256-byte aligned parts:
+ * the call's state (range flag, counters, the gallery's largest norm); the squared norms and norms
+ * of q and g (4 (Q + G) bytes each); the sample's norms; the column records (16 bytes per gallery
+ * row, padded to 256 rows); one pass's tile list; per pass of query rows the sample bounds
+ * (4 bytes x sample items per row), the survivor lists (8 x 4096 bytes per row), counters,
+ * widths, thresholds and row records; and the fp16 copies of q and g, zero-padded to the GEMM
+ * tile (rows to 256, D to 64).  Queries go through in passes of
+ * min(round_up(Q, 256), clamp(2^30 / per-row bytes, 256, 65536) rounded down to 256) rows: a pure
+ * function of the shapes, and no term grows with Q x G.
+ * Features must be finite.  Every refusal happens before any HIP call.  Q = 0 is a no-op.  No
+ * allocation or synchronisation inside. */
+int reidmi_search_prefilter_applies(int64_t Q, int64_t G, int64_t D, int k, int sample_stride);
+int64_t reidmi_search_prefiltered_workspace_bytes(int64_t Q, int64_t G, int64_t D, int k, int sample_stride);
+int reidmi_search_prefiltered_f32(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G, int64_t ldg,
+                                  int64_t D, int k, const int64_t* q_pids, const int64_t* q_cams,
+                                  const int64_t* g_pids, const int64_t* g_cams, const float* bound_dist,
+                                  const int32_t* bound_idx, int64_t ldb, int64_t index_base, int32_t* out_idx,
+                                  float* out_dist, int64_t ldo, int sample_stride, int32_t* need, int32_t* stats,
+                                  void* ws, int64_t ws_bytes, void* stream);
 
 /* Joins S partial rank lists per query into one: the lists of a gallery searched in blocks, or
  * on several GPUs a shard each.  List s of query i is in_idx[s*list_stride + i*ldi + 0..k_in) with

@@ -4,6 +4,7 @@
 // (rr_sample_kernel, rank_select_sv_kernel), plus the fp16 feature copy and the norm maxima they
 // need.  Called only from rerank_rank.hip (backend.h); the selection helpers are select.h's.
 #include "backend.h"
+#include "prefilter.h"
 #include "select.h"
 
 #include <cmath>
@@ -39,49 +40,7 @@ namespace reidmi {
 // candidate lists overflow, or with a non-finite bound or
 // max, is marked in need[] for the exact rows (reranking.HipStages.rank_rows runs them through
 // the exact distance kernel + selection).
-constexpr int DE_UNROLL = 16;
-
-__device__ __forceinline__ float dist_exact(const float* __restrict__ feat, int64_t ldf, int D,
-                                            const float* __restrict__ sqn, int64_t i, int64_t c) {
-    const float* a = feat + i * ldf;
-    const float* b = feat + c * ldf;
-    float acc = 0.0f;
-    int k = 0;
-    if ((ldf & 3) == 0) {
-        // unrolled so that many row loads are in flight ahead of the (sequential) fma chain
-#pragma unroll DE_UNROLL
-        for (; k + 4 <= D; k += 4) {
-            const float4 x = *(const float4*)(a + k), y = *(const float4*)(b + k);
-            acc = __builtin_fmaf(x.x, y.x, acc);
-            acc = __builtin_fmaf(x.y, y.y, acc);
-            acc = __builtin_fmaf(x.z, y.z, acc);
-            acc = __builtin_fmaf(x.w, y.w, acc);
-        }
-    }
-    for (; k < D; k++) acc = __builtin_fmaf(a[k], b[k], acc);
-    return __builtin_fmaf(-2.0f, acc, sqn[i] + sqn[c]);
-}
-
-__device__ __forceinline__ float block_max(float v, float* red) {
-    v = wave_max(v);
-    if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = v;
-    __syncthreads();
-    float m = red[0];
-    for (int w = 1; w < (int)(blockDim.x >> 6); w++) m = fmaxf(m, red[w]);
-    __syncthreads();
-    return m;
-}
-
-// Width of the pair bound of row i: hi(i, j) - (exact distance lower bound) <= w_i for every j,
-// from the largest norm and squared norm over the items (e is increasing in both; the margin
-// covers the roundings of hi, of fl(dt - e) and of this subtraction, each <= 2^-24 of
-// magnitudes <= 2.2 (s_i + s_max)).  For L2-normalised features (every n_j = 1) it is 2 e + a
-// few ulps, the width of the per-pair bound.
-__device__ __forceinline__ float rr_width(float s_i, float n_i, float n_max, float s_max, float c_rel, float c_abs,
-                                          float c_d) {
-    const float e = 1.01f * (__builtin_fmaf(c_rel * n_i, n_max, 0x1p-23f * (s_i + s_max)) + c_abs * (n_i + n_max) + c_d);
-    return 2.0f * e * (1.0f + 0x1p-10f) + 0x1p-20f * (s_i + s_max + e);
-}
+// (dist_exact, block_max and rr_width: prefilter.h, shared with the pre-filtered search)
 
 // Keep the entries j of idx[0, n) with keep(j) (order preserved, in place); one full wave.
 template <typename KEEP>
@@ -384,8 +343,6 @@ int rank_select_launch(float* dot, int64_t ldd, const float* feat, int64_t ldf, 
 //     order by od = d / rowmax): the same rank_out / rowmax bits.
 // A row whose list overflows RR_SV_CAP, holds a non-finite bound, or whose candidate lists
 // exceed rank_select1's capacities is marked in need[] for the exact rows, as before.
-constexpr int RR_SV_CAP = 4096;
-
 __global__ __launch_bounds__(256) void rr_sample_kernel(const float* __restrict__ hs, int64_t lds, int64_t ns,
                                                         const float* __restrict__ sqn, const float* __restrict__ nrm,
                                                         const float* __restrict__ nmax2, int64_t row0, int K,

@@ -14,6 +14,7 @@
 #include <algorithm>
 #include "backend.h"
 #include "gemm.h"
+#include "prefilter.h"
 #include "rerank.h"
 
 namespace reidmi {
@@ -110,7 +111,7 @@ __global__ void gather_rows_kernel(const float* __restrict__ x, int64_t ldx, int
 // (profiles/r03/rerank_1m_in_epilogue.txt).  Staged in LDS: 3.7 s for all row passes; over
 // the symmetric product's upper triangle (each pair tested for both its rows, one call):
 // 1.98 s, the 1M re-rank 7.1 -> 4.3 s (profiles/r03/rerank_1m_triangle.txt).
-constexpr int RR_SAMPLE_STRIDE = 16, RR_SV_CAP_ = 4096;
+constexpr int RR_SV_CAP_ = RR_SV_CAP;  // (prefilter.h, with RR_SAMPLE_STRIDE)
 
 __global__ void rr_gather_norms_kernel(const float* __restrict__ sqn, const float* __restrict__ nrm, int64_t ns,
                                        int S, float* __restrict__ sqn_s, float* __restrict__ nrm_s) {
@@ -142,6 +143,29 @@ __global__ void rr_rect_tiles_kernel(int tm, int tn, int* __restrict__ out) {
     const int rows = tm - b * RR_BAND < RR_BAND ? tm - b * RR_BAND : RR_BAND;
     const int nt = r / rows, mt = b * RR_BAND + r - nt * rows;
     out[t] = mt << 16 | nt;
+}
+
+// prefilter.h's launchers of the three kernels above (the pre-filtered search shares them)
+int rr_gather_norms_launch(const float* sqn, const float* nrm, int64_t ns, int S, float* sqn_s, float* nrm_s,
+                           hipStream_t s) {
+    hipLaunchKernelGGL(rr_gather_norms_kernel, dim3((unsigned)ceil_div(ns, 256)), dim3(256), 0, s, sqn, nrm, ns, S,
+                       sqn_s, nrm_s);
+    RM_LAUNCHED();
+    return OK;
+}
+
+int rr_colrec_launch(const float* sqn, const float* nrm, int64_t N, int64_t Np, void* out, hipStream_t s) {
+    hipLaunchKernelGGL(rr_colrec_kernel, dim3((unsigned)ceil_div(Np, 256)), dim3(256), 0, s, sqn, nrm, N, Np,
+                       (float4*)out);
+    RM_LAUNCHED();
+    return OK;
+}
+
+int rr_rect_tiles_launch(int tm, int tn, int* out, hipStream_t s) {
+    hipLaunchKernelGGL(rr_rect_tiles_kernel, dim3((unsigned)ceil_div((int64_t)tm * tn, 256)), dim3(256), 0, s, tm, tn,
+                       out);
+    RM_LAUNCHED();
+    return OK;
 }
 
 __host__ __device__ inline int64_t rr_tri_band_count(int T, int b) {
@@ -179,7 +203,6 @@ __global__ void rr_tri_tiles_kernel(int T, int* __restrict__ out) {
 // the epilogue's DMA reads them by tile).  Triangle (all rows in one call): the records of all
 // items, the sample's norms, the tile list, the counters and widths, and the survivor lists of
 // all rows (the sample bounds of a pass of rows overlay the lists before they are written).
-static int64_t rr_sv_ns(int64_t N, int S) { return S >= 2 ? N / S / 256 * 256 : 0; }
 static int64_t rr_sv_row_bytes(int64_t ns) { return 4 * ns + 8 * (int64_t)RR_SV_CAP_ + 4 + 4 + 16; }
 // rows per pass of the rectangular form in a chunk of chunk_rows x Np floats (0: not applicable)
 static int64_t rr_sv_pass_rows(int64_t N, int64_t Np, int64_t chunk_rows, int K, int S) {
@@ -222,19 +245,25 @@ static int tri_init(const float* sqn, const float* nrm, int64_t N, int64_t Np, i
 static int tri_sample(const _Float16* x16, int64_t Dp, const float* sqn, const float* nrm, const float* nmax2,
                       int64_t D, int K, int S, const float* sqn_s, const float* nrm_s, int64_t ns, int64_t a,
                       int64_t nb, float* hs, float4* meta, float* wrow, int32_t* cnt, int cap, hipStream_t s) {
+    // the sample: W rows = every S-th item (row stride S * Dp)
+    int r = rr_hi_sample_launch(x16 + a * Dp, Dp, x16, (int64_t)S * Dp, sqn, nrm, a, nb, sqn_s, nrm_s, ns, D, hs, s);
+    return r ? r : rr_sample_launch(hs, ns, ns, sqn, nrm, nmax2, a, nb, K, (int)D, meta, wrow, cnt, cap, s);
+}
+
+int rr_hi_sample_launch(const void* a16, int64_t Dp, const void* w16, int64_t ldw, const float* rsqn,
+                        const float* rnrm, int64_t row0, int64_t nb, const float* sqn_s, const float* nrm_s,
+                        int64_t ns, int64_t D, float* hs, hipStream_t s) {
     EpiArgs es{};
     es.out = hs;
     es.ldc = ns;
-    es.rr_sqn = sqn;
-    es.rr_nrm = nrm;
+    es.rr_sqn = rsqn;
+    es.rr_nrm = rnrm;
     es.rr_csqn = sqn_s;
     es.rr_cnrm = nrm_s;
-    es.rr_row0 = a;
+    es.rr_row0 = row0;
     es.rr_n = ns;
     rank_select_consts((int)D, es.rr_c);
-    // the sample: W rows = every S-th item (row stride S * Dp)
-    int r = gemm_f16(EPI_RRHI, x16 + a * Dp, Dp, x16, (int64_t)S * Dp, nb, ns, Dp, es, s);
-    return r ? r : rr_sample_launch(hs, ns, ns, sqn, nrm, nmax2, a, nb, K, (int)D, meta, wrow, cnt, cap, s);
+    return gemm_f16(EPI_RRHI, a16, Dp, w16, ldw, nb, ns, Dp, es, s);
 }
 
 // the survivor GEMM (EPI_RRSV) over tiles [0, ntiles) of a tile list; tri: the list is (part
@@ -243,24 +272,31 @@ static int tri_sample(const _Float16* x16, int64_t Dp, const float* sqn, const f
 static int tri_survivors(const _Float16* x16, int64_t Dp, int64_t Np, const float* sqn, const float* nrm, int64_t N,
                          int64_t D, int64_t a, int64_t M, const float4* rowmeta, const float4* colrec, const int* tiles,
                          int64_t ntiles, bool tri, int32_t* cnt, int2* list, int cap, hipStream_t s) {
+    // (the epilogue takes the items' norms from the records: sqn / nrm are not passed on)
+    (void)sqn;
+    (void)nrm;
+    return rr_survivors_launch(x16 + a * Dp, x16, Dp, Np, N, D, M, rowmeta, colrec, tiles, ntiles, tri, cnt, list, cap,
+                               s);
+}
+
+int rr_survivors_launch(const void* a16, const void* w16, int64_t Dp, int64_t Np, int64_t N, int64_t D, int64_t M,
+                        const void* rowmeta, const void* colrec, const int* tiles, int64_t ntiles, bool tri,
+                        int32_t* cnt, void* list, int cap, hipStream_t s) {
     if (ntiles <= 0) return OK;
     EpiArgs ev{};
-    ev.rr_sqn = sqn;
-    ev.rr_nrm = nrm;
-    ev.rr_row0 = a;
     ev.rr_n = N;
     rank_select_consts((int)D, ev.rr_c);
-    ev.rr_rowmeta = rowmeta;
-    ev.rr_colrec = colrec;
+    ev.rr_rowmeta = (const float4*)rowmeta;
+    ev.rr_colrec = (const float4*)colrec;
     ev.rr_tiles = tiles;
     ev.rr_ntiles = ntiles;
     ev.rr_tri = tri;
     ev.sv_cnt = cnt;
-    ev.sv_list = list;
+    ev.sv_list = (int2*)list;
     ev.sv_cap = cap;
     GemmOpts persistent;
     persistent.tile = 2;  // the survivor epilogue's LDS buffers live in the 256 x 256 tile
-    return gemm_f16(EPI_RRSV, x16 + a * Dp, Dp, x16, Dp, M, Np, Dp, ev, s, persistent);
+    return gemm_f16(EPI_RRSV, a16, Dp, w16, Dp, M, Np, Dp, ev, s, persistent);
 }
 
 // rows per sample pass of the triangle form when its hs scratch overlays the N x cap lists

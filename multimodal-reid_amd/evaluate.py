@@ -116,7 +116,8 @@ def _max_dist_rows(what, max_dist, Q):
     return t.to(torch.float32)
 
 
-def search_device(qf, gf, k, q_pids=None, q_camids=None, g_pids=None, g_camids=None, with_dist=True, max_dist=None):
+def search_device(qf, gf, k, q_pids=None, q_camids=None, g_pids=None, g_camids=None, with_dist=True, max_dist=None,
+                  prefilter=False, return_stats=False, _sample_stride=0):
     """The k nearest gallery rows of every query row (reidmi_search_f32: the selection runs in the
     distance kernel's epilogue, no (Q,G) matrix): (idx int32 [Q][k], dist fp32 [Q][k] or None) on the
     GPU, bit for bit euclidean_distance_device + topk_rows_device.  With the four label arrays, gallery
@@ -126,7 +127,16 @@ def search_device(qf, gf, k, q_pids=None, q_camids=None, g_pids=None, g_camids=N
     only items at a distance <= max_dist of their query are ranked (reidmi_search_bounded_f32's radius
     form: the limit is the kernel's first threshold, nothing is filtered afterwards).  Rows are padded
     with -1 / +inf, so (idx >= 0).sum(1) is the number of hits, up to k; a query with nothing within
-    its radius gets an all-padded row.  A NaN or -inf radius admits nothing."""
+    its radius gets an all-padded row.  A NaN or -inf radius admits nothing.
+    prefilter (default False): the same lists, bit for bit, through reidmi_search_prefiltered_f32: an
+    fp16 MFMA product bounds every distance, and only the few items per row that can still be among
+    the k nearest are computed exactly.  Where the pre-filter does not apply (a small gallery or D:
+    reidmi_search_prefilter_applies) the exact search runs instead; rows it cannot decide (distances
+    too concentrated, features beyond fp16's range) are searched exactly afterwards.  Reading how many
+    such rows there are is this path's one synchronisation with the GPU.  Faster on large galleries,
+    slower on small ones.
+    return_stats: also return a dict: applied (the pre-filtered call ran), need_rows (rows it left to
+    the exact search), max_survivors, rescored (exact distances it computed), range_failed."""
     tau = _max_dist_rows("search", max_dist, qf.shape[0])
     qf, gf = _as_dev_f32(qf), _as_dev_f32(gf)
     Q, D = qf.shape
@@ -140,8 +150,12 @@ def search_device(qf, gf, k, q_pids=None, q_camids=None, g_pids=None, g_camids=N
     idx = torch.empty((Q, max(k, 0)), device=qf.device, dtype=torch.int32)
     dist = torch.empty((Q, max(k, 0)), device=qf.device, dtype=torch.float32) if with_dist else None
     bound = None if tau is None else (tau.to(qf.device).contiguous(), None, 1, 0)
-    _search_into(qf, gf, k, (qp, qc, gp, gc), idx, dist, max(k, 1), bound)
-    return idx, dist
+    stats = dict(_NO_PREFILTER)
+    if prefilter:
+        stats = _search_prefiltered_into(qf, gf, k, (qp, qc, gp, gc), idx, dist, max(k, 1), bound, _sample_stride)
+    else:
+        _search_into(qf, gf, k, (qp, qc, gp, gc), idx, dist, max(k, 1), bound)
+    return (idx, dist, stats) if return_stats else (idx, dist)
 
 
 def _search_into(qf, gf, k, labels, idx, dist, ldo, bound=None):
@@ -162,9 +176,48 @@ def _search_into(qf, gf, k, labels, idx, dist, ldo, bound=None):
               ldo, _lib.ptr(ws), nb, _lib.stream())
 
 
-def search(qf, gf, k, q_pids=None, q_camids=None, g_pids=None, g_camids=None, with_dist=True, max_dist=None):
+_NO_PREFILTER = {"applied": False, "need_rows": 0, "max_survivors": 0, "rescored": 0, "range_failed": 0}
+
+
+def _search_prefiltered_into(qf, gf, k, labels, idx, dist, ldo, bound=None, sample_stride=0):
+    """_search_into through reidmi_search_prefiltered_f32 (same arguments; idx / dist are [Q][>= k]
+    tensors of pitch ldo): the exact search where the pre-filter does not apply, else the pre-filtered
+    call, then the exact search of the rows it marked in need, scattered back.  Returns search_device's
+    stats dict.  stats.tolist() below is the one synchronisation."""
+    Q, D = qf.shape
+    G = gf.shape[0]
+    L = _lib.load()
+    if Q == 0 or not L.reidmi_search_prefilter_applies(Q, G, D, k, sample_stride):
+        _search_into(qf, gf, k, labels, idx, dist, ldo, bound)
+        return dict(_NO_PREFILTER)
+    nb = L.reidmi_search_prefiltered_workspace_bytes(Q, G, D, k, sample_stride)
+    ws = torch.empty(nb, device=qf.device, dtype=torch.uint8)
+    need = torch.empty(Q, device=qf.device, dtype=torch.int32)
+    stats = torch.empty(4, device=qf.device, dtype=torch.int32)
+    bd, bi, ldb, base = (None, None, 1, 0) if bound is None else bound
+    _lib.call("reidmi_search_prefiltered_f32", _lib.ptr(qf), Q, qf.stride(0), _lib.ptr(gf), G, gf.stride(0), D, k,
+              *(_lib.ptr(a) for a in labels), _lib.ptr(bd), _lib.ptr(bi), ldb, base, _lib.ptr(idx), _lib.ptr(dist),
+              ldo, sample_stride, _lib.ptr(need), _lib.ptr(stats), _lib.ptr(ws), nb, _lib.stream())
+    st = stats.tolist()
+    if st[0]:
+        rows = torch.nonzero(need).squeeze(1)
+        n = rows.numel()
+        sub_lab = labels if labels[0] is None else (labels[0][rows], labels[1][rows], labels[2], labels[3])
+        sub_bound = None if bound is None else (bd[rows].contiguous(), None if bi is None else bi[rows].contiguous(),
+                                                1, base)
+        sidx = torch.empty((n, k), device=qf.device, dtype=torch.int32)
+        sdist = None if dist is None else torch.empty((n, k), device=qf.device, dtype=torch.float32)
+        _search_into(qf[rows].contiguous(), gf, k, sub_lab, sidx, sdist, k, sub_bound)
+        idx[rows, :k] = sidx
+        if dist is not None:
+            dist[rows, :k] = sdist
+    return {"applied": True, "need_rows": st[0], "max_survivors": st[1], "rescored": st[2], "range_failed": st[3]}
+
+
+def search(qf, gf, k, q_pids=None, q_camids=None, g_pids=None, g_camids=None, with_dist=True, max_dist=None,
+           prefilter=False):
     """search_device, returned as numpy arrays."""
-    idx, dist = search_device(qf, gf, k, q_pids, q_camids, g_pids, g_camids, with_dist, max_dist)
+    idx, dist = search_device(qf, gf, k, q_pids, q_camids, g_pids, g_camids, with_dist, max_dist, prefilter)
     return idx.cpu().numpy(), (dist.cpu().numpy() if with_dist else None)
 
 
@@ -222,10 +275,14 @@ class SearchAccumulator:
     rows padded with -1 / +inf as search_device(max_dist=) pads them.  It bounds the first block (the
     radius form) and, with carry_bound, every row whose carried list is not yet full; a full row's
     k-th key is at or below the radius, so it is the tighter bound and takes over.  No block is ever
-    searched under a bound that admits more than the radius."""
+    searched under a bound that admits more than the radius.
+    prefilter (default False): every block's search goes through search_device(prefilter=True)'s
+    path, the carried bound and the radius as its bound arguments; a block too small for the
+    pre-filter takes the exact search.  The result is the same, bit for bit."""
 
     def __init__(self, qf, k, q_pids=None, q_camids=None, with_dist=True, carry_bound=CARRY_BOUND_DEFAULT,
-                 max_dist=None):
+                 max_dist=None, prefilter=False, _sample_stride=0):
+        self.prefilter, self._sample_stride = bool(prefilter), int(_sample_stride)
         if not isinstance(carry_bound, (bool, np.bool_)):
             raise _lib.ReidmiError("SearchAccumulator: carry_bound must be True or False")
         tau = _max_dist_rows("SearchAccumulator", max_dist, qf.shape[0])
@@ -263,7 +320,11 @@ class SearchAccumulator:
         if kb < self.k:  # the search writes [0, kb) of a row
             self._idx[slot].fill_(-1)
             self._dist[slot].fill_(float("inf"))
-        _search_into(self.qf, gf, kb, lab, self._idx[slot], self._dist[slot], self.k, self._bound())
+        if self.prefilter:
+            _search_prefiltered_into(self.qf, gf, kb, lab, self._idx[slot], self._dist[slot], self.k, self._bound(),
+                                     self._sample_stride)
+        else:
+            _search_into(self.qf, gf, kb, lab, self._idx[slot], self._dist[slot], self.k, self._bound())
         if self.count:
             c = self._carried
             lo = min(c, 1)  # lists lo and lo + 1
@@ -296,20 +357,20 @@ class SearchAccumulator:
 
 
 def search_blocks_device(qf, blocks, k, q_pids=None, q_camids=None, with_dist=True,
-                         carry_bound=CARRY_BOUND_DEFAULT, max_dist=None):
+                         carry_bound=CARRY_BOUND_DEFAULT, max_dist=None, prefilter=False):
     """SearchAccumulator over ``blocks``: an iterable of feature blocks or, with query labels, of
     (features, g_pids, g_camids) tuples.  Bit for bit search_device over their concatenation (with
-    the same max_dist), whatever carry_bound is."""
-    acc = SearchAccumulator(qf, k, q_pids, q_camids, with_dist, carry_bound, max_dist)
+    the same max_dist), whatever carry_bound and prefilter are."""
+    acc = SearchAccumulator(qf, k, q_pids, q_camids, with_dist, carry_bound, max_dist, prefilter)
     for b in blocks:
         acc.add(*b) if isinstance(b, (tuple, list)) else acc.add(b)
     return acc.result()
 
 
 def search_blocks(qf, blocks, k, q_pids=None, q_camids=None, with_dist=True, carry_bound=CARRY_BOUND_DEFAULT,
-                  max_dist=None):
+                  max_dist=None, prefilter=False):
     """search_blocks_device, returned as numpy arrays."""
-    idx, dist = search_blocks_device(qf, blocks, k, q_pids, q_camids, with_dist, carry_bound, max_dist)
+    idx, dist = search_blocks_device(qf, blocks, k, q_pids, q_camids, with_dist, carry_bound, max_dist, prefilter)
     return idx.cpu().numpy(), (dist.cpu().numpy() if with_dist else None)
 
 
@@ -1213,7 +1274,7 @@ class R1_mAP_eval():
         self._print(cmc, mAP)
         return cmc, mAP
 
-    def rank_lists(self, k=10, remove_same_cam=True):
+    def rank_lists(self, k=10, remove_same_cam=True, prefilter=False):
         """The ranked lists behind compute()'s scores (SURVEY.md §8e "top-max_rank rank lists for
         output"): numpy (idx int32 [num_query][k], dist fp32 [num_query][k]) of the query rows against
         the gallery rows, features normalised as compute() does, nearest first, ties by gallery index;
@@ -1227,7 +1288,9 @@ class R1_mAP_eval():
         order against the rank-ordered gallery, bit for bit the single-process lists.  The Euclidean
         lists come from search_sharded (every rank searches its own gallery shard, the ranks exchange
         lists, not features); the re-ranked ones gather features and labels as compute() does (the
-        k-reciprocal stages need the whole gallery) and shard the rows (re_ranking_search(sharded=True))."""
+        k-reciprocal stages need the whole gallery) and shard the rows (re_ranking_search(sharded=True)).
+        prefilter: the single-process Euclidean lists through search(prefilter=True), the same lists
+        bit for bit; the re-ranked and sharded paths do not take it."""
         from . import distributed as rd
         self._check_expansion()
         feats = torch.cat(self.feats, dim=0)
@@ -1257,7 +1320,7 @@ class R1_mAP_eval():
             if self.reranking:
                 from .reranking import re_ranking_search
                 return re_ranking_search(feats[:nq], feats[nq:], k, 50, 15, 0.3, *lab)
-            return search(feats[:nq], feats[nq:], k, *lab)
+            return search(feats[:nq], feats[nq:], k, *lab, prefilter=prefilter)
 
     def pair_stats(self, edges=None):
         """pair_stats (numpy) of the query rows against the gallery rows on the features and labels
