@@ -1054,9 +1054,24 @@ int reidmi_preprocess_lds_size(int oh, int ow, int max_h, int max_w, int64_t* by
  * the device, info = the HOST info[10] of the plan call (B must equal info[9]); ws >= info[1]
  * bytes; pix >= info[2] bytes receives the HWC uint8 images; err int32 [B] (device) = the plan
  * status, or 5 where the entropy-coded data does not decode (that image's coefficients are
- * then zero). */
+ * then zero).
+ *
+ * reidmi_jpeg_plan_ex (HOST only) is reidmi_jpeg_plan with a flags word; flags = 0 is
+ * reidmi_jpeg_plan itself.  REIDMI_JPEG_PROGRESSIVE also plans progressive files (SOF2, Huffman,
+ * 8-bit, the same component layouts): every scan kind of the format (DC / AC, first /
+ * refinement, interleaved or not, restart intervals, tables redefined between scans), bit-exact
+ * with Pillow.  The planner then walks such a file to its EOI: status 6 when it ends before
+ * (Pillow: "image file is truncated"), 2 when its scans do not deliver every coefficient of
+ * every component to full precision (libjpeg smooths such images; that is not reproduced), 1
+ * for scan parameters libjpeg rejects.  The plan lists each progressive image's scans, and the
+ * high 32 bits of info[5] count those images: reidmi_jpeg_decode (unchanged signature) then
+ * runs one more kernel for them and none when there are none.  Sequential files get the same
+ * status, meta and pixels with either flags value. */
+#define REIDMI_JPEG_PROGRESSIVE 1
 int reidmi_jpeg_plan(const uint8_t* files, const int64_t* offsets, int64_t B, void* plan, int64_t plan_capacity,
                      int64_t* meta, int32_t* status, int64_t* info);
+int reidmi_jpeg_plan_ex(const uint8_t* files, const int64_t* offsets, int64_t B, int flags, void* plan,
+                        int64_t plan_capacity, int64_t* meta, int32_t* status, int64_t* info);
 int reidmi_jpeg_decode(const uint8_t* files, const void* plan, const int64_t* info, int64_t B, void* ws,
                        int64_t ws_bytes, uint8_t* pix, int32_t* err, void* stream);
 

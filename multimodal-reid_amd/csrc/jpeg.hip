@@ -13,13 +13,18 @@
 //          jpeg_pixels_kernel  — one workgroup per image: islow IDCT of every block into its
 //                                component plane (L2-resident), then fancy upsampling +
 //                                YCbCr->RGB per output pixel.
-// Supported: baseline / extended-sequential Huffman, 8-bit, one scan, grayscale or three
-// components at 4:4:4, 4:2:2 or 4:2:0 (every ReID benchmark's crops).  Anything else gets a
-// per-image status and is left to the caller (the Python mirror raises).
+//          jpeg_progressive_kernel — one lane per progressive image (reidmi_jpeg_plan_ex with
+//                                REIDMI_JPEG_PROGRESSIVE only): every scan of jdphuff.c, in file
+//                                order, into the same coefficient blocks (cleared first).
+// Supported: baseline / extended-sequential Huffman, 8-bit, one scan — and, opt-in, progressive
+// (SOF2) Huffman, 8-bit, whose scans deliver every coefficient to full precision — grayscale or
+// three components at 4:4:4, 4:2:2 or 4:2:0 (every ReID benchmark's crops).  Anything else gets
+// a per-image status and is left to the caller (the Python mirror raises).
 #include <algorithm>
 #include <cstring>
 #include <string>
 #include <thread>
+#include <unordered_map>
 #include <vector>
 
 #include "common.h"
@@ -72,16 +77,27 @@ struct Pools {
     std::vector<std::string> huff_raw;   // 16 counts + symbols of each pooled table
     std::vector<int16_t> quant;          // [n][64]
 
+    std::unordered_map<std::string, int> huff_index;   // raw table -> pool index, for large pools
+
     // Tables repeat across a dataset (one encoder setting: 4 Huffman + 2 quantisation tables),
-    // so the lookup is a scan of the few pooled ones, newest first.
+    // so the lookup is a scan of the few newest pooled ones.  Progressive files carry optimised
+    // tables of their own, one per scan: beyond kNewest the lookup goes through the index.
+    static constexpr int kNewest = 8;
     int add_huff(const uint8_t* raw, int len) {
-        for (int i = (int)huff_raw.size() - 1; i >= 0; --i)
+        const int n = (int)huff_raw.size();
+        for (int i = n - 1; i >= 0 && i >= n - kNewest; --i)
             if ((int)huff_raw[i].size() == len && memcmp(huff_raw[i].data(), raw, len) == 0) return i;
+        std::string key((const char*)raw, (size_t)len);
+        if (n > kNewest) {
+            const auto it = huff_index.find(key);
+            if (it != huff_index.end()) return it->second;
+        }
         JpegHuff t;
         build_huff(raw, raw + 16, len - 16, t);
         huff.push_back(t);
-        huff_raw.emplace_back((const char*)raw, len);
-        return (int)huff.size() - 1;
+        huff_index.emplace(key, n);
+        huff_raw.push_back(std::move(key));
+        return n;
     }
     int add_quant(const int16_t* q) {
         for (int i = (int)(quant.size() / 64) - 1; i >= 0; --i)
@@ -133,9 +149,25 @@ static const uint8_t kStdAcChroma[178] = {
     0xf9, 0xfa,
 };
 
-// jdmarker.c read_markers up to the first SOS, restricted to what the device decodes.
-static int32_t parse_one(const uint8_t* f, int64_t n, int64_t base, JpegImage& im, Pools& pools) {
+constexpr int kPlanProgressive = 1;   // REIDMI_JPEG_PROGRESSIVE
+constexpr int kMaxScans = 256;        // per image (a scan script needs far fewer); more: J_UNSUPPORTED
+
+// jdmarker.c read_markers up to the first SOS, restricted to what the device decodes.  With
+// kPlanProgressive a progressive (SOF2) file is walked to its EOI instead: every SOS adds a
+// JpegScan to `scans` (tables as the DHT segments before it left them), the entropy-coded data is
+// skipped by searching for the next marker that is no RSTn, and a file that ends before EOI is
+// J_TRUNCATED (libjpeg absorbs every scan before any output, so its input starves).
+static int32_t parse_walk(const uint8_t* f, int64_t n, int64_t base, JpegImage& im, Pools& pools, int flags,
+                          std::vector<JpegScan>& scans) {
     memset(&im, 0, sizeof(im));   // (status is set by the caller from the return value)
+    const size_t scan_base = scans.size();
+    bool prog = false;
+    // the data ends: before the first scan the file is no JPEG, after it libjpeg's input starves
+    const auto cut = [&] { return scans.size() > scan_base ? J_TRUNCATED : J_NOT_JPEG; };
+    int8_t coef_bits[3][64];   // jdphuff.c coef_bits: the last Al of each coefficient, -1 = not yet seen
+    memset(coef_bits, -1, sizeof(coef_bits));
+    bool qlatched[3] = {false, false, false};   // jdinput.c latch_quant_tables: a component keeps the
+    int16_t ql[3][64];                          // table that was current at its first scan
     // Pillow's JpegImagePlugin accepts only files starting FF D8 FF (_accept)
     if (n < 4 || f[0] != 0xFF || f[1] != 0xD8 || f[2] != 0xFF) return J_NOT_JPEG;
     int64_t p = 2;
@@ -150,22 +182,34 @@ static int32_t parse_one(const uint8_t* f, int64_t n, int64_t base, JpegImage& i
     for (;;) {
         while (p < n && f[p] != 0xFF) ++p;   // extraneous bytes (libjpeg warns and skips)
         while (p < n && f[p] == 0xFF) ++p;   // fill bytes
-        if (p >= n) return J_NOT_JPEG;
+        if (p >= n) return cut();
         const int m = f[p++];
         if (m == 0x00) continue;   // 0xFF 0x00: skipped like garbage (next_marker)
         // markers outside Pillow's table (TEM, 0x02-0xBF): JpegImagePlugin "no marker found"
         if (m < 0xC0) return J_NOT_JPEG;
         if (m >= 0xD0 && m <= 0xD7) continue;   // RSTn: no parameters
         if (m == 0xD8) return J_NOT_JPEG;   // a second SOI (get_soi: JERR_SOI_DUPLICATE)
-        if (m == 0xD9) return J_NOT_JPEG;   // EOI before any scan
+        if (m == 0xD9) {
+            if (scans.size() == scan_base) return J_NOT_JPEG;   // EOI before any scan
+            // libjpeg smooths between blocks where a scan script stops short of full precision:
+            // not reproduced, so any coefficient not delivered down to Al = 0 refuses the file
+            for (int c = 0; c < im.ncomp; ++c)
+                for (int k = 0; k < 64; ++k)
+                    if (coef_bits[c][k] != 0) return J_UNSUPPORTED;
+            break;
+        }
         // DHP, EXP, JPGn: skipped by Pillow's parser, then libjpeg's JERR_UNKNOWN_MARKER
         if (m == 0xDE || m == 0xDF || (m >= 0xF0 && m <= 0xFD)) return J_NOT_JPEG;
-        if (p + 2 > n) return J_NOT_JPEG;
+        if (p + 2 > n) return cut();
         const int len = u16be(f + p);
-        if (len < 2 || p + len > n) return J_NOT_JPEG;
+        if (len < 2) return J_NOT_JPEG;
+        if (p + len > n) return cut();
         const uint8_t* s = f + p + 2;
         const int sl = len - 2;
-        if (m == 0xC0 || m == 0xC1) {   // SOF0 baseline / SOF1 extended sequential, Huffman
+        if (m == 0xC0 || m == 0xC1 || (m == 0xC2 && (flags & kPlanProgressive))) {
+            // SOF0 baseline / SOF1 extended sequential / SOF2 progressive (opt-in), Huffman
+            if (prog || (sof && m == 0xC2)) return J_NOT_JPEG;   // get_sof: JERR_SOF_DUPLICATE
+            prog = m == 0xC2;
             if (sl < 6 || s[0] != 8) return J_UNSUPPORTED;
             im.h = u16be(s + 1);
             im.w = u16be(s + 3);
@@ -228,6 +272,70 @@ static int32_t parse_one(const uint8_t* f, int64_t n, int64_t base, JpegImage& i
             if (!sof) return J_NOT_JPEG;
             const int ns = sl > 0 ? s[0] : 0;
             if (len != 2 * ns + 6) return J_NOT_JPEG;   // get_sos: JERR_BAD_LENGTH
+            if (prog) {
+                // get_sos: JERR_BAD_LENGTH outside 1..4; more selectors than frame components
+                // cannot all name a component once (JERR_BAD_COMPONENT_ID), and ci[] holds 3
+                if (ns < 1 || ns > im.ncomp) return J_NOT_JPEG;
+                if ((int)(scans.size() - scan_base) >= kMaxScans) return J_UNSUPPORTED;
+                JpegScan sc;
+                memset(&sc, 0, sizeof(sc));
+                int seen = 0;
+                for (int j = 0; j < ns; ++j) {   // get_sos: each selector names a frame component, once
+                    int c = -1;
+                    for (int k = 0; k < im.ncomp && c < 0; ++k)
+                        if (cid[k] == s[1 + 2 * j] && !(seen >> k & 1)) c = k;
+                    if (c < 0) return J_NOT_JPEG;   // JERR_BAD_COMPONENT_ID
+                    seen |= 1 << c;
+                    sc.ci[j] = c;
+                }
+                sc.ns = ns;
+                sc.ss = s[1 + 2 * ns];
+                sc.se = s[2 + 2 * ns];
+                sc.ah = s[3 + 2 * ns] >> 4;
+                sc.al = s[3 + 2 * ns] & 15;
+                sc.ri = im.ri;
+                // jdphuff.c start_pass_phuff_decoder: JERR_BAD_PROGRESSION
+                const bool dc_scan = sc.ss == 0;
+                bool bad = dc_scan ? sc.se != 0 : (sc.ss > sc.se || sc.se > 63 || ns != 1);
+                if (sc.ah != 0 && sc.al != sc.ah - 1) bad = true;
+                if (sc.al > 13) bad = true;
+                if (bad) return J_NOT_JPEG;
+                for (int j = 0; j < ns; ++j) {
+                    const int c = sc.ci[j];
+                    // (an Ah that is not the band's previous Al is libjpeg's JWRN_BOGUS_PROGRESSION
+                    // warning: it goes on)
+                    for (int k = sc.ss; k <= sc.se; ++k) coef_bits[c][k] = (int8_t)sc.al;
+                    if (!qlatched[c]) {
+                        if (!qdef[tq[c]]) return J_BAD_TABLE;   // JERR_NO_QUANT_TABLE
+                        memcpy(ql[c], qt[tq[c]], sizeof(ql[c]));
+                        qlatched[c] = true;
+                    }
+                    if (dc_scan && sc.ah != 0) continue;   // DC refinement: raw bits, no table
+                    const int tn = dc_scan ? s[2 + 2 * j] >> 4 : s[2 + 2 * j] & 15;
+                    if (tn > 3) return J_BAD_TABLE;   // jpeg_make_d_derived_tbl: JERR_NO_HUFF_TABLE
+                    const uint8_t** tab = dc_scan ? hdc : hac;
+                    int* tab_len = dc_scan ? hdc_len : hac_len;
+                    if (!tab[tn] && tn < 2) {   // jpeg_std_huff_table
+                        tab[tn] = dc_scan ? (tn ? kStdDcChroma : kStdDcLuma) : (tn ? kStdAcChroma : kStdAcLuma);
+                        tab_len[tn] = dc_scan ? (int)sizeof(kStdDcLuma) : (int)sizeof(kStdAcLuma);
+                    }
+                    if (!tab[tn] || !huff_ok(tab[tn], tab[tn] + 16, tab_len[tn] - 16, dc_scan)) return J_BAD_TABLE;
+                    (dc_scan ? sc.dc : sc.ac)[j] = pools.add_huff(tab[tn], tab_len[tn]);
+                }
+                // the entropy-coded data: up to the next marker that is no RSTn (jdmarker.c next_marker
+                // skips what a scan leaves over in the same way)
+                const uint8_t *q = f + p + len, *at, *after;
+                int mk;
+                do {
+                    if (!LjInput::next_marker(q, f + n, &at, &mk, &after)) return J_TRUNCATED;
+                    q = after;
+                } while (mk >= 0xD0 && mk <= 0xD7);
+                sc.src_off = base + p + len;
+                sc.src_len = (at - f) - (p + len);
+                scans.push_back(sc);
+                p = at - f;
+                continue;
+            }
             if (ns != im.ncomp || sl < 4 + 2 * ns) return J_UNSUPPORTED;   // one interleaved scan only
             for (int j = 0; j < ns; ++j) {
                 if (s[1 + 2 * j] != cid[j]) return J_UNSUPPORTED;   // scan order = frame order
@@ -256,9 +364,17 @@ static int32_t parse_one(const uint8_t* f, int64_t n, int64_t base, JpegImage& i
         }
         p += len;
     }
-    for (int c = 0; c < im.ncomp; ++c) {
-        if (!qdef[tq[c]]) return J_BAD_TABLE;
-        im.quant[c] = pools.add_quant(qt[tq[c]]);
+    if (prog) {   // (complete coef_bits: every component had a scan, so its table is latched)
+        for (int c = 0; c < im.ncomp; ++c) im.quant[c] = pools.add_quant(ql[c]);
+        im.scan0 = (int32_t)scan_base;
+        im.nscan = (int32_t)(scans.size() - scan_base);
+        im.src_off = base;
+        im.src_len = n;
+    } else {
+        for (int c = 0; c < im.ncomp; ++c) {
+            if (!qdef[tq[c]]) return J_BAD_TABLE;
+            im.quant[c] = pools.add_quant(qt[tq[c]]);
+        }
     }
     // geometry (jdinput.c initial_setup, per_scan_setup)
     if (im.ncomp == 1) {
@@ -291,6 +407,18 @@ static int32_t parse_one(const uint8_t* f, int64_t n, int64_t base, JpegImage& i
     }
     if ((int64_t)im.w * im.h > (int64_t)1 << 26) return J_UNSUPPORTED;   // > 64 Mpixel
     return J_OK;
+}
+
+// A file that fails leaves no scans behind.
+static int32_t parse_one(const uint8_t* f, int64_t n, int64_t base, JpegImage& im, Pools& pools, int flags,
+                         std::vector<JpegScan>& scans) {
+    const size_t scan_base = scans.size();
+    const int32_t st = parse_walk(f, n, base, im, pools, flags, scans);
+    if (st != J_OK) {   // (a refused image is a sequential one to the kernels: the entropy pass reports its status)
+        scans.resize(scan_base);
+        im.scan0 = im.nscan = 0;
+    }
+    return st;
 }
 
 static inline int64_t align_up(int64_t v, int64_t a) { return (v + a - 1) / a * a; }
@@ -345,6 +473,7 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restr
     const int64_t i = (int64_t)blockIdx.x * 64 + threadIdx.x;
     if (i >= B) return;
     const JpegImage im = ((const JpegImage*)(plan + P->img_off))[i];
+    if (im.status == J_OK && im.nscan != 0) return;   // a planned progressive image: jpeg_progressive_kernel decodes it and writes err[i]
     int32_t st = im.status;
     if (st == J_OK) {
         LdsSink sink{blocks[threadIdx.x], nullptr};
@@ -365,6 +494,43 @@ __global__ __launch_bounds__(64) void jpeg_entropy_kernel(const uint8_t* __restr
             uint4* d = (uint4*)(coef + im.coef_off);
             for (int64_t j = 0; j < n / 8; ++j) d[j] = make_uint4(0, 0, 0, 0);
         }
+    }
+    err[i] = st;
+}
+
+// Progressive images (the plan's prog[] list; launched only when there are any).  Their scans
+// add to coefficients already in the workspace, so it is cleared first — those images' ranges
+// only: the sequential path writes every block whole and relies on not clearing.
+__global__ __launch_bounds__(256) void jpeg_progressive_zero_kernel(const uint8_t* __restrict__ plan,
+                                                                    int16_t* __restrict__ coef) {
+    const JpegPlan* P = (const JpegPlan*)plan;
+    if ((int64_t)blockIdx.x >= P->n_prog) return;
+    const int64_t i = ((const int32_t*)(plan + P->prog_off))[blockIdx.x];
+    const JpegImage* im = (const JpegImage*)(plan + P->img_off) + i;
+    int64_t n = 0;
+    for (int c = 0; c < im->ncomp; ++c) n += (int64_t)im->bw[c] * im->bh[c] * 64;
+    uint4* d = (uint4*)(coef + im->coef_off);   // (whole blocks of 128 bytes)
+    for (int64_t j = threadIdx.x; j < n / 8; j += 256) d[j] = make_uint4(0, 0, 0, 0);
+}
+
+// One lane per progressive image, walking its scans in file order (the refinement scans depend
+// on the earlier ones); Huffman lookups go to the plan's table pool in global memory (a table
+// per scan: the pool of a batch does not fit LDS).
+__global__ __launch_bounds__(64) void jpeg_progressive_kernel(const uint8_t* __restrict__ src,
+                                                              const uint8_t* __restrict__ plan, int16_t* coef,
+                                                              int32_t* __restrict__ err) {
+    const JpegPlan* P = (const JpegPlan*)plan;
+    const int64_t j = (int64_t)blockIdx.x * 64 + threadIdx.x;
+    if (j >= P->n_prog) return;
+    const int64_t i = ((const int32_t*)(plan + P->prog_off))[j];
+    const JpegImage im = ((const JpegImage*)(plan + P->img_off))[i];
+    int32_t st = progressive_decode(src, im, (const JpegScan*)(plan + P->scan_off),
+                                    (const JpegHuff*)(plan + P->huff_off), coef);
+    if (st != J_OK) {   // undecodable data: the image's coefficients are defined as zero
+        int64_t n = 0;
+        for (int c = 0; c < im.ncomp; ++c) n += (int64_t)im.bw[c] * im.bh[c] * 64;
+        uint4* d = (uint4*)(coef + im.coef_off);
+        for (int64_t k = 0; k < n / 8; ++k) d[k] = make_uint4(0, 0, 0, 0);
     }
     err[i] = st;
 }
@@ -438,8 +604,14 @@ using namespace reidmi::jpeg;
 
 REIDMI_API int reidmi_jpeg_plan(const uint8_t* files, const int64_t* offsets, int64_t B, void* plan,
                                 int64_t plan_capacity, int64_t* meta, int32_t* status, int64_t* info) {
+    return reidmi_jpeg_plan_ex(files, offsets, B, 0, plan, plan_capacity, meta, status, info);
+}
+
+REIDMI_API int reidmi_jpeg_plan_ex(const uint8_t* files, const int64_t* offsets, int64_t B, int flags, void* plan,
+                                   int64_t plan_capacity, int64_t* meta, int32_t* status, int64_t* info) {
     RM_REQUIRE(B >= 0 && info != nullptr && (B == 0 || (files && offsets && meta && status)),
                "reidmi_jpeg_plan: bad arguments");
+    RM_REQUIRE((flags & ~kPlanProgressive) == 0, "reidmi_jpeg_plan_ex: unknown flags");
     for (int64_t i = 0; i < B; ++i)
         RM_REQUIRE(offsets[i] >= 0 && offsets[i + 1] >= offsets[i], "reidmi_jpeg_plan: offsets must be non-decreasing from 0");
     std::vector<JpegImage> imgs((size_t)B);
@@ -447,10 +619,12 @@ REIDMI_API int reidmi_jpeg_plan(const uint8_t* files, const int64_t* offsets, in
     const int nt = (int)std::max<int64_t>(1, std::min<int64_t>({16, (int64_t)std::thread::hardware_concurrency(),
                                                                B / 2048}));
     std::vector<Pools> local((size_t)nt);
+    std::vector<std::vector<JpegScan>> lscans((size_t)nt);   // progressive images' scans, per chunk
     auto work = [&](int t) {
         for (int64_t i = B * t / nt; i < B * (t + 1) / nt; ++i) {
             const int64_t a = offsets[i];
-            imgs[(size_t)i].status = parse_one(files + a, offsets[i + 1] - a, a, imgs[(size_t)i], local[(size_t)t]);
+            imgs[(size_t)i].status = parse_one(files + a, offsets[i + 1] - a, a, imgs[(size_t)i], local[(size_t)t],
+                                               flags, lscans[(size_t)t]);
         }
     };
     if (nt == 1) {
@@ -468,6 +642,21 @@ REIDMI_API int reidmi_jpeg_plan(const uint8_t* files, const int64_t* offsets, in
             hmap[(size_t)t].push_back(pools.add_huff((const uint8_t*)L.huff_raw[j].data(), (int)L.huff_raw[j].size()));
         for (size_t j = 0; j < L.quant.size() / 64; ++j) qmap[(size_t)t].push_back(pools.add_quant(L.quant.data() + 64 * j));
     }
+    std::vector<JpegScan> scans;
+    std::vector<int64_t> sbase((size_t)nt);
+    for (int t = 0; t < nt; ++t) {
+        sbase[(size_t)t] = (int64_t)scans.size();
+        for (JpegScan sc : lscans[(size_t)t]) {
+            const bool dc_first = sc.ss == 0 && sc.ah == 0, ac = sc.ss != 0;
+            for (int j = 0; j < sc.ns; ++j) {
+                if (dc_first) sc.dc[j] = hmap[(size_t)t][(size_t)sc.dc[j]];
+                if (ac) sc.ac[j] = hmap[(size_t)t][(size_t)sc.ac[j]];
+            }
+            scans.push_back(sc);
+        }
+    }
+    RM_REQUIRE(scans.size() < ((size_t)1 << 31), "reidmi_jpeg_plan_ex: too many scans in one batch");
+    std::vector<int32_t> prog;
     int64_t coef = 0, plane = 0, outb = 0, max_h = 0, max_w = 0, bad = 0, max_plane = 0;
     for (int64_t i = 0; i < B; ++i) {
         JpegImage& im = imgs[(size_t)i];
@@ -481,9 +670,15 @@ REIDMI_API int reidmi_jpeg_plan(const uint8_t* files, const int64_t* offsets, in
         int t = 0;
         while (t + 1 < nt && i >= B * (t + 1) / nt) ++t;
         for (int c = 0; c < im.ncomp; ++c) {
-            im.dc[c] = hmap[(size_t)t][(size_t)im.dc[c]];
-            im.ac[c] = hmap[(size_t)t][(size_t)im.ac[c]];
+            if (!im.nscan) {
+                im.dc[c] = hmap[(size_t)t][(size_t)im.dc[c]];
+                im.ac[c] = hmap[(size_t)t][(size_t)im.ac[c]];
+            }
             im.quant[c] = qmap[(size_t)t][(size_t)im.quant[c]];
+        }
+        if (im.nscan) {
+            im.scan0 += (int32_t)sbase[(size_t)t];
+            prog.push_back((int32_t)i);
         }
         im.coef_off = coef;
         im.plane_off = plane;
@@ -514,13 +709,18 @@ REIDMI_API int reidmi_jpeg_plan(const uint8_t* files, const int64_t* offsets, in
     hdr.coef_elems = coef;
     hdr.plane_bytes = plane;
     hdr.out_bytes = outb;
-    const int64_t plan_bytes = hdr.quant_off + hdr.n_quant * 128;
+    hdr.n_scan = (int64_t)scans.size();
+    hdr.n_prog = (int64_t)prog.size();
+    hdr.scan_off = align_up(hdr.quant_off + hdr.n_quant * 128, 64);
+    hdr.prog_off = hdr.scan_off + hdr.n_scan * (int64_t)sizeof(JpegScan);
+    // (a plan without progressive images ends after the quantisers, as it always has)
+    const int64_t plan_bytes = hdr.n_prog ? hdr.prog_off + hdr.n_prog * 4 : hdr.quant_off + hdr.n_quant * 128;
     info[0] = plan_bytes;
     info[1] = align_up(coef * 2, 256) + plane;   // workspace: int16 coefficients, then planes
     info[2] = outb;
     info[3] = max_h;
     info[4] = max_w;
-    info[5] = bad;
+    info[5] = bad + (hdr.n_prog << 32);   // (the high half tells reidmi_jpeg_decode to launch the progressive kernels)
     info[6] = coef;
     info[7] = hdr.n_huff;
     info[8] = max_plane;
@@ -532,6 +732,10 @@ REIDMI_API int reidmi_jpeg_plan(const uint8_t* files, const int64_t* offsets, in
     if (B) memcpy(pb + hdr.img_off, imgs.data(), (size_t)B * sizeof(JpegImage));
     if (hdr.n_huff) memcpy(pb + hdr.huff_off, pools.huff.data(), pools.huff.size() * sizeof(JpegHuff));
     if (hdr.n_quant) memcpy(pb + hdr.quant_off, pools.quant.data(), pools.quant.size() * sizeof(int16_t));
+    if (hdr.n_prog) {
+        memcpy(pb + hdr.scan_off, scans.data(), scans.size() * sizeof(JpegScan));
+        memcpy(pb + hdr.prog_off, prog.data(), prog.size() * sizeof(int32_t));
+    }
     return OK;
 }
 
@@ -551,6 +755,15 @@ REIDMI_API int reidmi_jpeg_decode(const uint8_t* files, const void* plan, const 
     else
         jpeg_entropy_kernel<false><<<eg, dim3(64), 0, s>>>(files, (const uint8_t*)plan, B, coef, err);
     RM_LAUNCHED();
+    const int64_t n_prog = info[5] >> 32;   // progressive images (reidmi_jpeg_plan_ex): none launches nothing
+    if (n_prog > 0) {
+        RM_REQUIRE(n_prog <= B, "reidmi_jpeg_decode: info[5] names more progressive images than B");
+        jpeg_progressive_zero_kernel<<<dim3((unsigned)n_prog), dim3(256), 0, s>>>((const uint8_t*)plan, coef);
+        RM_LAUNCHED();
+        jpeg_progressive_kernel<<<dim3((unsigned)((n_prog + 63) / 64)), dim3(64), 0, s>>>(files, (const uint8_t*)plan,
+                                                                                           coef, err);
+        RM_LAUNCHED();
+    }
     if (info[8] <= kPlaneLds)
         jpeg_pixels_kernel<true><<<dim3((unsigned)B), dim3(256), (size_t)info[8], s>>>((const uint8_t*)plan, coef,
                                                                                        planes, pix);

@@ -1,6 +1,6 @@
-// jpeg_core.h — baseline-JPEG decode arithmetic shared by the device kernels (jpeg.hip) and
-// the host-side check tool (tools/jpeg_host_check.hip).  What it reproduces, bit for bit, is
-// the decoder behind the reference's `Image.open(path).convert("RGB")` (data_prepare.py:89):
+// jpeg_core.h — JPEG decode arithmetic (baseline, and progressive where the plan asks for it)
+// shared by the device kernels (jpeg.hip) and the host-side check tool
+// (tools/jpeg_host_check.hip).  What it reproduces, bit for bit, is the decoder behind the reference's `Image.open(path).convert("RGB")` (data_prepare.py:89):
 // Pillow 12.2 on libjpeg-turbo (jpeg 6.2 API) with its defaults — Huffman sequential decode,
 // the "islow" integer IDCT (LL&M, 13-bit constants, 2 extra bits between passes), "fancy"
 // triangular chroma upsampling for 2x1 and 2x2 subsampling, and the 16-bit fixed-point
@@ -9,7 +9,9 @@
 //
 // A decode plan (built on the host by reidmi_jpeg_plan from the file headers) is one
 // position-independent blob: JpegPlan | JpegImage[B] | JpegHuff[n_huff] | int16 quant[n_quant][64]
-// (quantisers, like the coefficients, in zig-zag order).
+// | JpegScan[n_scan] | int32 prog[n_prog] (quantisers, like the coefficients, in zig-zag order;
+// the last two only where reidmi_jpeg_plan_ex planned progressive images: their scans, in file
+// order, and the indices of those images).
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
@@ -54,12 +56,25 @@ struct JpegImage {
     int32_t dw[3], dh[3];       // downsampled component size (libjpeg downsampled_width/height)
     int32_t quant[3], dc[3], ac[3];   // pool indices
     int32_t cid[3];             // frame component identifiers (the post-scan SOS checks)
+    int32_t scan0, nscan;       // progressive (SOF2) image: its JpegScan rows; nscan = 0: one sequential scan
+};                              // (then src_off / src_len are the whole file and ri is unused)
+
+struct JpegScan {               // one scan of a progressive image (jdphuff.c)
+    int64_t src_off, src_len;   // its entropy-coded data in the file batch: after the SOS header, up
+                                // to the next marker that is no RSTn
+    int32_t ns, ss, se, ah, al; // components in the scan, spectral band, successive approximation
+    int32_t ri;                 // restart interval in force (MCUs of this scan)
+    int32_t ci[3];              // frame component index of each scan component, in scan order
+    int32_t dc[3], ac[3];       // pool indices (dc: DC first scans, ac: AC scans; else 0)
+    int32_t pad;
 };
 
 struct JpegPlan {
     int64_t B, n_huff, n_quant;
     int64_t img_off, huff_off, quant_off;   // bytes from the plan start
     int64_t coef_elems, plane_bytes, out_bytes;
+    int64_t scan_off, n_scan;   // progressive images' scans
+    int64_t prog_off, n_prog;   // int32 indices of the progressive images
 };
 
 // natural (row-major) index -> zig-zag position.  Coefficients and quantisers are kept in
@@ -230,7 +245,29 @@ struct BitReader {
         bits -= l;
         return t->val[(c + t->valoff[l]) & 0xFF];
     }
+    // decode() for the progressive scans: -1 where the bits match no code of the table (the
+    // image then ends with J_BAD_DATA instead of libjpeg's warning and symbol 0)
+    __host__ __device__ inline int decode_strict(const JpegHuff* t) {
+        const uint32_t e = t->lut[acc >> (64 - kLookahead)];
+        if (e >> 8) {
+            const int l = (int)(e >> 8);
+            acc <<= l;
+            bits -= l;
+            return (int)(e & 0xFF);
+        }
+        const uint32_t code16 = (uint32_t)(acc >> 48);
+        int l = kLookahead + 1;
+#pragma unroll
+        for (int j = kLookahead + 1; j <= 16; ++j) l += code16 >= t->lim[j] ? 1 : 0;
+        if (l > 16) return -1;
+        const int32_t c = (int32_t)(code16 >> (16 - l));
+        acc <<= l;
+        bits -= l;
+        return t->val[(c + t->valoff[l]) & 0xFF];
+    }
 };
+
+__host__ __device__ inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 
 __host__ __device__ inline int32_t huff_extend(uint32_t v, int s) {   // HUFF_EXTEND
     return (v < (1u << (s - 1))) ? (int32_t)v - (1 << s) + 1 : (int32_t)v;
@@ -625,6 +662,217 @@ __host__ __device__ inline int32_t entropy_decode(const uint8_t* src, const Jpeg
     return post_scan_status(q, br.end, im);
 }
 
+// ---------------------------------------------------------------- progressive scans (one image)
+// jdphuff.c: the four scan kinds of a progressive (SOF2) image — DC first / DC refinement
+// (interleaved or not), AC first / AC refinement (one component, band Ss..Se, EOB runs) — decoded
+// scan after scan into the image's zeroed coefficient blocks; the refinement scans read and
+// modify what the earlier ones wrote.  An interleaved scan walks the image's MCU grid; a
+// single-component scan walks the ceil(dw / 8) x ceil(dh / 8) blocks of that component in raster
+// order (jdinput.c per_scan_setup), not the MCU-padded grid.  The host planner has walked every
+// marker of the file up to EOI (so libjpeg's input, which absorbs all scans before any output,
+// does not starve), validated each scan's parameters and checked that the scans deliver every
+// coefficient to full precision.
+__host__ __device__ inline int32_t pick3(const int32_t (&a)[3], int c) { return c == 0 ? a[0] : (c == 1 ? a[1] : a[2]); }
+
+// The bit source of one scan.  With restart intervals libjpeg's input position decides where the
+// search for RSTn starts, so its slow-path fetches (jdphuff.c has no fast path) are replayed
+// beside the decode (LjInput), as entropy_decode<true> does.
+struct ScanBits {
+    BitReader br;
+    LjInput lj;
+    bool replay;
+    __host__ __device__ inline void start(const uint8_t* b, const uint8_t* e, bool restarts) {
+        replay = restarts;
+        br.start(b, e);
+        lj.starved = false;
+        lj.fast = false;
+        lj.next_rst = 0;   // (get_sos resets next_restart_num)
+        lj.start(b, e);
+    }
+    // HUFF_DECODE: the symbol, or -1 for a code the table does not have
+    __host__ __device__ inline int symbol(const JpegHuff* t) {
+        br.refill();
+        const int64_t c0 = br.consumed();
+        if (replay) lj.need(c0, 8);
+        const int s = br.decode_strict(t);
+        if (replay) {
+            const int64_t c1 = br.consumed();
+            if (c1 - c0 > 8) lj.need_long(c0, (int)(c1 - c0));
+        }
+        return s;
+    }
+    __host__ __device__ inline uint32_t get(int n) {   // get_bits(n), n in [1, 16]
+        br.refill();
+        if (replay) lj.need(br.consumed(), n);
+        return br.take(n);
+    }
+    // process_restart: the buffered bits are discarded and the input continues after the RSTn
+    // libjpeg finds.  Returns whether a marker is left unread (insufficient_data is kept then).
+    __host__ __device__ inline bool restart() {
+        const bool unread = lj.restart();
+        br.start(lj.p, lj.end);
+        if (unread) {
+            br.marker = true;
+            br.real = 0;
+            br.nw_ok = false;
+        }
+        return unread;
+    }
+};
+
+// decode_mcu_AC_first for one block; false: a bad Huffman code
+__host__ __device__ inline bool ac_first_block(ScanBits& sb, const JpegHuff* t, int16_t* blk, int ss, int se, int al,
+                                               uint32_t& eobrun) {
+    if (eobrun > 0) {   // the band is all zero in this block
+        --eobrun;
+        return true;
+    }
+    for (int k = ss; k <= se; ++k) {
+        int s = sb.symbol(t);
+        if (s < 0) return false;
+        const int r = s >> 4;
+        s &= 15;
+        if (s) {
+            k += r;
+            const int32_t v = huff_extend(sb.get(s), s);
+            // a run past the block: jpeg_natural_order[]'s extra entries map k 64.. to position 63
+            blk[k > 63 ? 63 : k] = (int16_t)(v * (1 << al));
+        } else if (r == 15) {
+            k += 15;   // ZRL
+        } else {       // EOBr: this block's band ends here, and that of the next eobrun blocks is zero
+            eobrun = 1u << r;
+            if (r) eobrun += sb.get(r);
+            --eobrun;
+            break;
+        }
+    }
+    return true;
+}
+
+// one correction bit for an already-nonzero coefficient (jdphuff.c decode_mcu_AC_refine)
+__host__ __device__ inline void refine_nonzero(ScanBits& sb, int16_t* c, int32_t p1) {
+    if (sb.get(1) && (*c & p1) == 0) *c = (int16_t)(*c >= 0 ? *c + p1 : *c - p1);
+}
+
+// decode_mcu_AC_refine for one block; false: a bad Huffman code
+__host__ __device__ inline bool ac_refine_block(ScanBits& sb, const JpegHuff* t, int16_t* blk, int ss, int se, int al,
+                                                uint32_t& eobrun) {
+    const int32_t p1 = 1 << al;
+    int k = ss;
+    if (eobrun == 0) {
+        for (; k <= se; ++k) {
+            int s = sb.symbol(t);
+            if (s < 0) return false;
+            int r = s >> 4;
+            s &= 15;
+            int32_t nv = 0;
+            if (s) {   // a newly nonzero coefficient (its size is always 1): one sign bit
+                nv = sb.get(1) ? p1 : -p1;
+            } else if (r != 15) {
+                eobrun = 1u << r;
+                if (r) eobrun += sb.get(r);
+                break;   // force end-of-band
+            }
+            // over already-nonzero coefficients (a correction bit each) and r still-zero ones
+            do {
+                int16_t* c = blk + k;
+                if (*c != 0) {
+                    refine_nonzero(sb, c, p1);
+                } else if (--r < 0) {
+                    break;   // the target zero coefficient
+                }
+                ++k;
+            } while (k <= se);
+            if (s) blk[k > 63 ? 63 : k] = (int16_t)nv;
+        }
+    }
+    if (eobrun > 0) {   // the rest of the band: correction bits only
+        for (; k <= se; ++k)
+            if (blk[k] != 0) refine_nonzero(sb, blk + k, p1);
+        --eobrun;
+    }
+    return true;
+}
+
+__host__ __device__ inline int32_t progressive_scan(const uint8_t* src, const JpegImage& im, const JpegScan& sc,
+                                                    const JpegHuff* huff, int16_t* coef) {
+    ScanBits sb;
+    // the scan's own byte range bounds every read: it ends at the marker after the scan, where
+    // libjpeg's input stops too (zeros are fed from there)
+    sb.start(src + sc.src_off, src + sc.src_off + sc.src_len, sc.ri != 0);
+    const int ns = sc.ns < 3 ? sc.ns : 3;
+    const bool single = ns == 1;
+    const bool dc_scan = sc.ss == 0, first = sc.ah == 0;
+    const int al = sc.al;
+    // the planner checked Ss <= Se <= 63; the band is clamped all the same: no index leaves the block
+    const int ss = clampi(sc.ss, 1, 63), se = clampi(sc.se, 0, 63);
+    const int c0 = clampi(sc.ci[0], 0, 2);
+    const int mcux = single ? (pick3(im.dw, c0) + 7) / 8 : im.mcux;
+    const int mcuy = single ? (pick3(im.dh, c0) + 7) / 8 : im.mcuy;
+    int16_t* base = coef + im.coef_off;
+    int32_t pred0 = 0, pred1 = 0, pred2 = 0;
+    uint32_t eobrun = 0;
+    int togo = sc.ri;
+    // jdphuff.c: once a step used bits past the segment's data, the MCU finishes on zero bits
+    // and the later MCUs of the segment are left as they are (insufficient_data)
+    bool skip = false;
+    for (int my = 0; my < mcuy; ++my) {
+        for (int mx = 0; mx < mcux; ++mx) {
+            if (sc.ri && togo == 0) {
+                togo = sc.ri;
+                pred0 = pred1 = pred2 = 0;
+                eobrun = 0;
+                if (!sb.restart()) skip = false;
+            }
+            for (int j = 0; j < ns; ++j) {
+                const int c = clampi(sc.ci[j], 0, 2);
+                const int nbx = single ? 1 : pick3(im.hs, c), nby = single ? 1 : pick3(im.vs, c);
+                const int bw = pick3(im.bw, c), bh = pick3(im.bh, c);
+                int16_t* comp = base + (c == 0 ? im.comp_coef[0] : (c == 1 ? im.comp_coef[1] : im.comp_coef[2]));
+                for (int by = 0; by < nby; ++by) {
+                    for (int bx = 0; bx < nbx; ++bx) {
+                        const int y = my * nby + by, x = mx * nbx + bx;
+                        if (y >= bh || x >= bw) continue;   // (never, for a plan of reidmi_jpeg_plan_ex)
+                        int16_t* blk = comp + ((int64_t)y * bw + x) * 64;
+                        if (dc_scan) {
+                            if (!first) {   // decode_mcu_DC_refine (reads on after insufficient_data: zeros change nothing)
+                                if (sb.get(1)) blk[0] = (int16_t)(blk[0] | (1 << al));
+                            } else if (!skip) {   // decode_mcu_DC_first
+                                const int s = sb.symbol(huff + sc.dc[j]);
+                                if (s < 0 || s > 15) return J_BAD_DATA;
+                                const uint32_t d = s ? (uint32_t)huff_extend(sb.get(s), s) : 0u;
+                                const uint32_t v = (uint32_t)(c == 0 ? pred0 : (c == 1 ? pred1 : pred2)) + d;
+                                pred0 = c == 0 ? (int32_t)v : pred0;
+                                pred1 = c == 1 ? (int32_t)v : pred1;
+                                pred2 = c == 2 ? (int32_t)v : pred2;
+                                blk[0] = (int16_t)(v << al);
+                            }
+                        } else if (!skip) {
+                            const bool ok = first ? ac_first_block(sb, huff + sc.ac[0], blk, ss, se, al, eobrun)
+                                                  : ac_refine_block(sb, huff + sc.ac[0], blk, ss, se, al, eobrun);
+                            if (!ok) return J_BAD_DATA;
+                        }
+                    }
+                }
+            }
+            skip = skip || sb.br.past_data();
+            --togo;
+        }
+    }
+    return J_OK;
+}
+
+// Every scan of a progressive image, in file order, into its coefficient blocks (zeroed by the
+// caller).  Returns J_OK or J_BAD_DATA (a bad Huffman code).
+__host__ __device__ inline int32_t progressive_decode(const uint8_t* src, const JpegImage& im, const JpegScan* scans,
+                                                      const JpegHuff* huff, int16_t* coef) {
+    for (int s = 0; s < im.nscan; ++s) {
+        const int32_t st = progressive_scan(src, im, scans[im.scan0 + s], huff, coef);
+        if (st != J_OK) return st;
+    }
+    return J_OK;
+}
+
 // ---------------------------------------------------------------- islow IDCT (jidctint.c)
 constexpr int CB = 13, P1 = 2;   // CONST_BITS, PASS1_BITS
 constexpr int32_t F0298 = 2446, F0390 = 3196, F0541 = 4433, F0765 = 6270, F0899 = 7373, F1175 = 9633,
@@ -757,7 +1005,6 @@ __host__ __device__ inline void idct_islow(const int16_t* coef, const int16_t* q
 }
 
 // ---------------------------------------------------------------- upsampling + colour
-__host__ __device__ inline int clampi(int v, int lo, int hi) { return v < lo ? lo : (v > hi ? hi : v); }
 __host__ __device__ inline uint8_t clamp8(int v) { return (uint8_t)clampi(v, 0, 255); }
 
 // One chroma sample of output pixel (x, y), component c with plane `pl` (pitch bw*8):

@@ -184,7 +184,9 @@ class JpegBatch:
     """Host side of a JPEG batch: the file bytes, the decode plan (reidmi_jpeg_plan) and the
     per-image status / (offset, h, w) of the decoded layout.  Host only: needs no GPU."""
 
-    def __init__(self, files, buffer=None, plan_out=None):
+    def __init__(self, files, buffer=None, plan_out=None, progressive=False):
+        # progressive: also plan progressive (SOF2) files (reidmi_jpeg_plan_ex with
+        # REIDMI_JPEG_PROGRESSIVE); False refuses them with status 2, as reidmi_jpeg_plan does;
         # buffer: (uint8 bytes, int64 offsets [B+1]) already joined by read_files (files unused);
         # plan_out: a uint8 array the plan is written into when it fits (the loader's pinned slot)
         self.buf, self.offsets = read_files(files) if buffer is None else buffer
@@ -203,10 +205,17 @@ class JpegBatch:
             self.plan = plan_out
         else:
             self.plan = np.zeros(cap, np.uint8)
-        _lib.call("reidmi_jpeg_plan", *args, self.plan.ctypes.data_as(ctypes.c_void_p), cap, *out)
+        self.progressive = bool(progressive)
+
+        def plan(dst, capacity):
+            if self.progressive:   # (a progressive image brings a table per scan: the second pass is usual then)
+                _lib.call("reidmi_jpeg_plan_ex", *args, 1, dst.ctypes.data_as(ctypes.c_void_p), capacity, *out)
+            else:
+                _lib.call("reidmi_jpeg_plan", *args, dst.ctypes.data_as(ctypes.c_void_p), capacity, *out)
+        plan(self.plan, cap)
         if int(self.info[0]) > cap:
             self.plan = np.zeros(int(self.info[0]), np.uint8)
-            _lib.call("reidmi_jpeg_plan", *args, self.plan.ctypes.data_as(ctypes.c_void_p), int(self.info[0]), *out)
+            plan(self.plan, int(self.info[0]))
         self.plan = self.plan[:int(self.info[0])]
         self.ws_bytes, self.out_bytes = int(self.info[1]), int(self.info[2])
         self.max_h, self.max_w = max(int(self.info[3]), 1), max(int(self.info[4]), 1)
@@ -220,14 +229,15 @@ class JpegBatch:
                              f"{JPEG_STATUS.get(int(st[i]), int(st[i]))}")
 
 
-def decode_jpeg(files, device=None, check=True, return_status=False):
+def decode_jpeg(files, device=None, check=True, return_status=False, progressive=False):
     """Image.open(f).convert("RGB") of every file (data_prepare.py:89), on the GPU.
     Returns (pix uint8 device tensor of the packed HWC images, meta int64 device tensor [B][3]
     = (offset, h, w), JpegBatch) — the input reidmi_preprocess_u8 takes — and, with
     return_status, the per-file device status (JPEG_STATUS codes).  With check=True an
-    unsupported or undecodable file raises (there is no host fallback)."""
+    unsupported or undecodable file raises (there is no host fallback).  progressive=True also
+    decodes progressive files (opt-in; a JpegBatch passed in carries its own choice)."""
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    jb = files if isinstance(files, JpegBatch) else JpegBatch(files)
+    jb = files if isinstance(files, JpegBatch) else JpegBatch(files, progressive=progressive)
     if check:
         jb.raise_for_status()
     dev_files = _to_device(jb.buf, device) if jb.buf.size else torch.zeros(1, dtype=torch.uint8, device=device)
@@ -245,13 +255,14 @@ def decode_jpeg(files, device=None, check=True, return_status=False):
     return (pix, meta, jb, err[:jb.B]) if return_status else (pix, meta, jb)
 
 
-def preprocess_jpeg(files, height=256, width=128, model_type="vit", dtype=torch.float16, device=None, out=None):
+def preprocess_jpeg(files, height=256, width=128, model_type="vit", dtype=torch.float16, device=None, out=None,
+                    progressive=False):
     """reidDataset.__getitem__ + transform_test for a batch of JPEG files, all on the GPU:
     decode_jpeg -> Resize -> ToTensor -> Normalize -> [B, 3, height, width]."""
     if dtype not in (torch.float32, torch.float16):
         raise ValueError("dtype must be torch.float32 or torch.float16")
     device = torch.device("cuda", torch.cuda.current_device()) if device is None else torch.device(device)
-    pix, meta, jb = decode_jpeg(files, device)
+    pix, meta, jb = decode_jpeg(files, device, progressive=progressive)
     B = jb.B
     if out is None:
         out = torch.empty((B, 3, height, width), dtype=dtype, device=device)
@@ -269,7 +280,8 @@ def preprocess_jpeg(files, height=256, width=128, model_type="vit", dtype=torch.
 
 def get_loader(dataset, batch_size, image_height, image_width, model_type, **kw):
     """data_prepare.py:256-284 on the device for an already-listed dataset (loader.get_loader):
-    (loader_gallery, loader_query, loader_gallery_augmented, loader_query_augmented)."""
+    (loader_gallery, loader_query, loader_gallery_augmented, loader_query_augmented).
+    progressive=True lets the loaders take progressive JPEG files too."""
     from .loader import get_loader as _get_loader
     return _get_loader(dataset, batch_size, image_height, image_width, model_type, **kw)
 

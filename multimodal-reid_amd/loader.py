@@ -106,7 +106,8 @@ class _Pipeline:
     """The shared source of a plain / augmented loader pair (see the module docstring)."""
 
     def __init__(self, items, batch_size, image_height, image_width, model_type, dtype, device, host_threads,
-                 depth, tta_seed, shard=None):
+                 depth, tta_seed, shard=None, progressive=False):
+        self.progressive = bool(progressive)
         if dtype not in (torch.float32, torch.float16):
             raise ValueError("dtype must be torch.float32 or torch.float16")
         items, tta = _shard_items(items, tta_seed, shard)
@@ -145,7 +146,8 @@ class _Pipeline:
         if buf.ctypes.data != slot.files.data_ptr():   # paths larger than the slot: stage a pinned copy
             slot.reserve(buf.size, 0, 0)
             slot.files.numpy()[:buf.size] = buf
-        jb = JpegBatch(None, buffer=(slot.files.numpy()[:buf.size], off), plan_out=slot.plan.numpy())
+        jb = JpegBatch(None, buffer=(slot.files.numpy()[:buf.size], off), plan_out=slot.plan.numpy(),
+                       progressive=self.progressive)
         jb.raise_for_status()
         slot.meta.numpy()[:3 * jb.B] = jb.meta.reshape(-1)
         return jb, slot
@@ -260,15 +262,15 @@ class DeviceLoader:
 
 
 def loader_pair(items, batch_size, image_height=256, image_width=128, model_type="vit", dtype=torch.float16,
-                device=None, host_threads=0, depth=2, tta_seed=0, shard=None):
+                device=None, host_threads=0, depth=2, tta_seed=0, shard=None, progressive=False):
     """(plain loader, augmented loader) over one item list, sharing one decode pipeline."""
     p = _Pipeline(items, batch_size, image_height, image_width, model_type, dtype, device, host_threads, depth,
-                  tta_seed, shard)
+                  tta_seed, shard, progressive)
     return DeviceLoader(p, False), DeviceLoader(p, True)
 
 
 def get_loader(dataset, batch_size, image_height, image_width, model_type, dtype=torch.float16, device=None,
-               host_threads=0, depth=2, tta_seed=0, shard=None):
+               host_threads=0, depth=2, tta_seed=0, shard=None, progressive=False):
     """data_prepare.py:256-284 for an already-listed dataset (`dataset.query`, `dataset.gallery`):
     returns (loader_gallery, loader_query, loader_gallery_augmented, loader_query_augmented),
     the reference's order.  `tta_seed` seeds the augmented views' RandomCrop offsets (gallery
@@ -276,9 +278,11 @@ def get_loader(dataset, batch_size, image_height, image_width, model_type, dtype
     walks this rank's contiguous shard of its list (one process per GPU; the items keep the
     offsets they have in one process) — feed the shards to get_cmc_map(..., sharded=True).
     `model_type` selects the normalisation statistics only (data_prepare.norm_stats: "vit" ->
-    0.5 / 0.5, anything else, e.g. "rn50" -> ImageNet's), as data_prepare.py:260,268."""
+    0.5 / 0.5, anything else, e.g. "rn50" -> ImageNet's), as data_prepare.py:260,268.
+    `progressive=True` also decodes progressive JPEG files (JpegBatch(progressive=True)); by
+    default one such file makes its batch raise."""
     g, ga = loader_pair(dataset.gallery, batch_size, image_height, image_width, model_type, dtype, device,
-                        host_threads, depth, tta_seed, shard)
+                        host_threads, depth, tta_seed, shard, progressive)
     q, qa = loader_pair(dataset.query, batch_size, image_height, image_width, model_type, dtype, device,
-                        host_threads, depth, None if tta_seed is None else tta_seed + 1, shard)
+                        host_threads, depth, None if tta_seed is None else tta_seed + 1, shard, progressive)
     return g, q, ga, qa

@@ -4,6 +4,7 @@
 // library; the GPU tests compare the device kernels with Pillow directly.
 //   hipcc -O2 -std=c++17 -fPIC -shared -I../multimodal-reid_amd/csrc -I../include \
 //         jpeg_host_check.hip -o build/libjpeghost.so
+#include <algorithm>
 #include <cstring>
 #include <vector>
 
@@ -25,9 +26,17 @@ static int host_decode(const uint8_t* files, const uint8_t* plan, const int64_t*
         const JpegImage& im = imgs[i];
         err[i] = im.status;
         if (im.status != J_OK) continue;
-        DirectSink sink;
-        err[i] = always_replay ? J_REPLAY : entropy_decode<false>(files, im, huff, coef.data(), sink);
-        if (err[i] == J_REPLAY) err[i] = entropy_decode<true>(files, im, huff, coef.data(), sink);
+        if (im.nscan) {   // a progressive image (reidmi_jpeg_plan_ex): what jpeg_progressive_kernel runs
+            int64_t n = 0;
+            for (int c = 0; c < im.ncomp; ++c) n += (int64_t)im.bw[c] * im.bh[c] * 64;
+            std::fill(coef.begin() + im.coef_off, coef.begin() + im.coef_off + n, (int16_t)0);
+            err[i] = progressive_decode(files, im, (const JpegScan*)(plan + P->scan_off), huff, coef.data());
+            if (err[i] != J_OK) std::fill(coef.begin() + im.coef_off, coef.begin() + im.coef_off + n, (int16_t)0);
+        } else {
+            DirectSink sink;
+            err[i] = always_replay ? J_REPLAY : entropy_decode<false>(files, im, huff, coef.data(), sink);
+            if (err[i] == J_REPLAY) err[i] = entropy_decode<true>(files, im, huff, coef.data(), sink);
+        }
         for (int c = 0; c < im.ncomp; ++c) {
             const int64_t pitch = (int64_t)im.bw[c] * 8;
             for (int by = 0; by < im.bh[c]; ++by)
