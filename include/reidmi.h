@@ -16,6 +16,8 @@
 #define REIDMI_H
 #include <stdint.h>
 
+#include "reidmi_filter.h"
+
 #ifdef __cplusplus
 extern "C" {
 #endif
@@ -37,7 +39,9 @@ const char* reidmi_last_error(void);
  * 11: reidmi_rr_jaccard_self_rows and reidmi_dbscan_jaccard added.
  * 12: reidmi_pair_stats_f32 added.
  * 13: reidmi_search_prefiltered_f32, reidmi_search_prefilter_applies and
- *     reidmi_search_prefiltered_workspace_bytes added. */
+ *     reidmi_search_prefiltered_workspace_bytes added.
+ * 14: reidmi_search_filter, reidmi_search_filtered_f32 and reidmi_search_prefiltered_filtered_f32
+ *     added. */
 int reidmi_abi_version(void);
 
 /* ------------------------------------------------------------ retrieval back end */
@@ -177,6 +181,56 @@ int reidmi_search_prefiltered_f32(const float* q, int64_t Q, int64_t ldq, const 
                                   const int32_t* bound_idx, int64_t ldb, int64_t index_base, int32_t* out_idx,
                                   float* out_dist, int64_t ldo, int sample_stride, int32_t* need, int32_t* stats,
                                   void* ws, int64_t ws_bytes, void* stream);
+
+/* Filtered search: which gallery items a query may match at all.  A host struct of DEVICE pointers;
+ * a clause whose pointers are all NULL is absent.  Gallery item j is admitted for query i iff every
+ * clause that is present holds (and the label rule of the four label arrays, when those are given):
+ *   valid        g_valid[j] != 0                                            (uint8 [G])
+ *   camera mask  0 <= g_cam[j] < 64 and bit g_cam[j] of q_cam_mask[i] is set
+ *                (int64 [G]; int64 [Q] read as 64 bits)
+ *   time window  q_time_lo[i] <= g_time[j] <= q_time_hi[i]                  (int64 [G], [Q], [Q])
+ *   group        g_group[j] != q_group[i]                                   (int64 [G], [Q])
+ * The clauses are joined by "and": their order does not matter.  The struct is reidmi_filter.h's
+ * (included above):
+ *     const uint8_t* g_valid;
+ *     const int64_t* g_cam;   const int64_t* q_cam_mask;
+ *     const int64_t* g_time;  const int64_t* q_time_lo;  const int64_t* q_time_hi;
+ *     const int64_t* g_group; const int64_t* q_group; */
+
+/* reidmi_search_bounded_f32 over the admitted items only: its arguments, with flt after the four
+ * label pointers.  The lists are, bit for bit, the rows of reidmi_distmat_f32 with the non-admitted
+ * entries removed, ranked by (distance, gallery index), cut at k and at the bound, padded with
+ * -1 / +inf: a query with fewer than k admitted items gets a short row, one with none an all-padded
+ * row.  The bound applies to admitted items only (a carried key is an admitted item's).  The clauses
+ * are tested in the kernel's epilogue behind the threshold compare (an item with g_valid == 0 is
+ * skipped before it), by the function that holds the label rule; nothing is filtered afterwards.
+ * flt == NULL, or every pointer in it NULL: reidmi_search_bounded_f32, bit for bit and kernel for
+ * kernel.  A half-given clause (g_cam without q_cam_mask, q_time_lo without q_time_hi or g_time,
+ * g_group without q_group, or the reverse) is refused with the clause's name in reidmi_last_error.
+ * The struct is read during the call; the arrays it points to must stay valid until the stream has
+ * run the call.  Workspace and every other rule: reidmi_search_bounded_f32's. */
+int reidmi_search_filtered_f32(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G, int64_t ldg,
+                               int64_t D, int k, const int64_t* q_pids, const int64_t* q_cams, const int64_t* g_pids,
+                               const int64_t* g_cams, const reidmi_search_filter* flt, const float* bound_dist,
+                               const int32_t* bound_idx, int64_t ldb, int64_t index_base, int32_t* out_idx,
+                               float* out_dist, int64_t ldo, void* ws, int64_t ws_bytes, void* stream);
+
+/* reidmi_search_prefiltered_f32 over the admitted items only: its arguments, with flt in the same
+ * position, its workspace (reidmi_search_prefiltered_workspace_bytes) and its need / stats.  The
+ * sample threshold is the k-th smallest bound among the ADMITTED sample items and a candidate must
+ * be admitted, so rows with need[i] == 0 hold reidmi_search_filtered_f32's bits; the caller runs
+ * reidmi_search_filtered_f32 with the same filter for the others.  The survivor lists hold admitted
+ * and non-admitted pairs alike, so a selective filter (few admitted sample items, a loose
+ * threshold) overflows them and marks many rows: correct, but then the exact call alone is faster.
+ * flt == NULL or all-NULL: reidmi_search_prefiltered_f32 bit for bit.  Half-given clauses are
+ * refused as above. */
+int reidmi_search_prefiltered_filtered_f32(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G,
+                                           int64_t ldg, int64_t D, int k, const int64_t* q_pids,
+                                           const int64_t* q_cams, const int64_t* g_pids, const int64_t* g_cams,
+                                           const reidmi_search_filter* flt, const float* bound_dist,
+                                           const int32_t* bound_idx, int64_t ldb, int64_t index_base,
+                                           int32_t* out_idx, float* out_dist, int64_t ldo, int sample_stride,
+                                           int32_t* need, int32_t* stats, void* ws, int64_t ws_bytes, void* stream);
 
 /* Joins S partial rank lists per query into one: the lists of a gallery searched in blocks, or
  * on several GPUs a shard each.  List s of query i is in_idx[s*list_stride + i*ldi + 0..k_in) with

@@ -42,6 +42,14 @@ int reidmi_search_bounded_f32_ex(const float* q, int64_t Q, int64_t ldq, const f
                                  const int32_t* bound_idx, int64_t ldb, int64_t index_base, int32_t* out_idx,
                                  float* out_dist, int64_t ldo, void* ws, int64_t ws_bytes, int splits, int cap,
                                  int32_t* stats, void* stream);
+/* reidmi_search_filtered_f32 with the same forced splits, capacity and counters (stats[1] counts
+ * the pairs that also passed the filter's clauses). */
+int reidmi_search_filtered_f32_ex(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G, int64_t ldg,
+                                  int64_t D, int k, const int64_t* q_pids, const int64_t* q_cams,
+                                  const int64_t* g_pids, const int64_t* g_cams, const reidmi_search_filter* flt,
+                                  const float* bound_dist, const int32_t* bound_idx, int64_t ldb, int64_t index_base,
+                                  int32_t* out_idx, float* out_dist, int64_t ldo, void* ws, int64_t ws_bytes,
+                                  int splits, int cap, int32_t* stats, void* stream);
 
 /* reidmi_gemm_f16 with an explicit tiling: tile 0 = auto (the persistent 256x256x64 LDS-DMA
  * tile for >= 256 tiles, else 128x128x64), 1 = force 128x128, 2 = force persistent; ngroups =

@@ -103,20 +103,27 @@ def _abi():
     def read(name):
         with open(os.path.join(build_lib.INCLUDE, name)) as f:
             return f.read()
-    types, product = parse_header(read("reidmi.h"))
+    ftypes, _ = parse_header(read("reidmi_filter.h"))  # reidmi.h includes it
+    types, product = parse_header(read("reidmi.h"), ftypes)
     _, tools = parse_header(read("reidmi_tools.h"), types)
-    return types, product, tools
+    return types, product, tools, ftypes
 
 
 def declarations(tools=False):
     """{entry point: (restype, argtypes)} of include/reidmi.h, with reidmi_tools.h's for tools."""
-    _, product, extra = _abi()
+    _, product, extra, _ = _abi()
     return dict(product, **extra) if tools else dict(product)
 
 
-def structs():
-    """{C struct name: its ctypes.Structure} of include/reidmi.h."""
-    return {n: t for n, t in _abi()[0].items() if isinstance(t, type) and issubclass(t, ctypes.Structure)}
+def structs(header="reidmi.h"):
+    """{C struct name: its ctypes.Structure} of the structs include/<header> itself defines:
+    reidmi.h (the model's weight and source structs) or reidmi_filter.h, which reidmi.h includes
+    (reidmi_search_filter)."""
+    types, _, _, ftypes = _abi()
+    if header not in ("reidmi.h", "reidmi_filter.h"):
+        raise ReidmiError(f"structs: no such header `{header}`")
+    own = ftypes if header == "reidmi_filter.h" else {n: t for n, t in types.items() if n not in ftypes}
+    return {n: t for n, t in own.items() if isinstance(t, type) and issubclass(t, ctypes.Structure)}
 
 
 def bind(cdll, tools=False):

@@ -26,4 +26,4 @@ REIDMI_API const char* reidmi_last_error(void) { return reidmi::g_err.c_str(); }
 // 12: pair statistics (reidmi_pair_stats_f32);
 // 13: pre-filtered search (reidmi_search_prefiltered_f32, reidmi_search_prefilter_applies,
 //     reidmi_search_prefiltered_workspace_bytes).
-REIDMI_API int reidmi_abi_version(void) { return 13; }
+REIDMI_API int reidmi_abi_version(void) { return 14; }

@@ -7,8 +7,11 @@
 //   reidmi_search_bounded_f32  the same under a per-query bound (a radius, or the k-th key of a
 //                          list carried from earlier gallery blocks): the bound is the initial
 //                          threshold of the row, so the epilogue filters against it from tile one
+//   reidmi_search_filtered_f32  the same over the items a filter admits (admit.h: validity, camera
+//                          mask, time window and group clauses next to the label rule)
 //
 // The distance tile is distance.h's (the distance kernels' bits), the selection select.h's.
+#include "admit.h"
 #include "backend.h"
 #include "distance.h"
 #include "select.h"
@@ -75,7 +78,10 @@ int topk_launch(const float* x, int64_t rows, int64_t cols, int64_t ldx, const f
 // (PIPE: a copy of dm_tile_pipe, else dm_tile_single, whose K-step is the distance kernels'
 // dm_kstep) and their v = dm_value, so v below has the distance kernel's bits, and selects in
 // the epilogue instead of storing:
-//   * (v, j) is kept when j passes the label predicate and key_less(v, j, thr[row]); thr[row]
+//   * (v, j) is kept when key_less(v, j, thr[row]) and j is admitted (admit.h sr_admit: the label
+//     rule and, in the FILTER instantiations, the filter's clauses; a column with g_valid == 0 is
+//     skipped before the compare, the other clauses' query side is read from global memory behind
+//     it, so the filtered kernel keeps the LDS below and four workgroups per CU); thr[row]
 //     is the row's bound (none: +inf) until K candidates were seen, then its current K-th key, in
 //     LDS, and only falls; s_own says which of the two it is (a bounded row that collects K
 //     candidates must still compact once, so that its own K-th key replaces the bound; one with
@@ -138,11 +144,11 @@ __device__ __forceinline__ void sr_compact_row(float2* __restrict__ list, uint64
     __builtin_amdgcn_wave_barrier();  // the scratch is free for the wave's next row
 }
 
-template <bool PIPE, bool LABELS>
+template <bool PIPE, bool LABELS, bool FILTER>
 __global__ __launch_bounds__(256, DM2_MINWG) void search_f32_kernel(
     const float* __restrict__ q, const float* __restrict__ g, const float* __restrict__ qq,
-    const float* __restrict__ gg, int64_t Q, int64_t G, int64_t D, int64_t ldq, int64_t ldg, int K, DmLabels lab,
-    SrBound bnd, int64_t range_len, int cap, float2* __restrict__ lists, int32_t* __restrict__ stats) {
+    const float* __restrict__ gg, int64_t Q, int64_t G, int64_t D, int64_t ldq, int64_t ldg, int K,
+    std::conditional_t<FILTER, SrFilter, SrLabels> flt, SrBound bnd, int64_t range_len, int cap, float2* __restrict__ lists, int32_t* __restrict__ stats) {
     __shared__ float smem[DM_SMEM];
     __shared__ float s_tv[DM_BM], s_qq[DM_BM];
     __shared__ int s_ti[DM_BM], s_cnt[DM_BM], s_own[DM_BM];
@@ -174,8 +180,8 @@ __global__ __launch_bounds__(256, DM2_MINWG) void search_f32_kernel(
         s_cnt[tid] = 0;
         s_qq[tid] = in ? qq[bm + tid] : 0.0f;
         if constexpr (LABELS) {
-            s_qp[tid] = in ? lab.qp[bm + tid] : 0;
-            s_qc[tid] = in ? lab.qc[bm + tid] : 0;
+            s_qp[tid] = in ? flt.qp[bm + tid] : 0;
+            s_qc[tid] = in ? flt.qc[bm + tid] : 0;
         }
     }
     __syncthreads();
@@ -256,8 +262,10 @@ __global__ __launch_bounds__(256, DM2_MINWG) void search_f32_kernel(
             for (int nt = 0; nt < 2; nt++) {
                 const int64_t j = bn + wn * 64 + nt * 32 + (lane & 31);
                 if (j >= c1) continue;
+                if constexpr (FILTER)
+                    if (!sr_item_valid(flt, j)) continue;  // the cheapest clause: the column's 32 rows at once
                 const float ggj = gg[j];
-                int64_t gpj = 0, gcj = 0;
+                SrItem item = {0, 0, 0, 0, 0, true};  // the gallery side, read once per column and lane
                 bool lab_loaded = false;
 #pragma unroll
                 for (int mt = 0; mt < 2; mt++)
@@ -269,9 +277,13 @@ __global__ __launch_bounds__(256, DM2_MINWG) void search_f32_kernel(
                         const float tv = s_tv[il];
                         if (!(v <= tv)) continue;
                         if (!key_less(v, (int)j, tv, s_ti[il])) continue;
-                        if constexpr (LABELS) {
-                            if (!lab_loaded) { gpj = lab.gp[j]; gcj = lab.gc[j]; lab_loaded = true; }
-                            if (gpj == s_qp[il] && gcj == s_qc[il]) continue;  // evaluate.py:46-48
+                        if constexpr (LABELS || FILTER) {
+                            if (!lab_loaded) { item = sr_item(flt, LABELS, FILTER, j); lab_loaded = true; }
+                            // the query side: the labels from LDS, the clauses' values from global
+                            // memory (L2: this is the rare path after the first tiles)
+                            SrRowRef row = {s_qp[LABELS ? il : 0], s_qc[LABELS ? il : 0], 0, 0, 0, 0};
+                            if constexpr (FILTER) sr_row_clauses(flt, bm + il, row);
+                            if (!sr_admit(flt, LABELS, FILTER, row, item)) continue;
                         }
                         const int p = atomicAdd(&s_cnt[il], 1);  // < cap: count + 128 <= cap before the tile
                         mylists[(int64_t)il * cap + p] = make_float2(v, __int_as_float((int)j));
@@ -388,16 +400,16 @@ static int64_t sr_ws_bytes(int64_t Q, int64_t G, const SrPlan& p) {
 
 int search_impl(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G, int64_t ldg, int64_t D, int k,
                 const int64_t* q_pids, const int64_t* q_cams, const int64_t* g_pids, const int64_t* g_cams,
-                const float* bound_dist, const int32_t* bound_idx, int64_t ldb, int64_t index_base, int32_t* out_idx,
-                float* out_dist, int64_t ldo, void* ws, int64_t ws_bytes, int splits, int cap, int32_t* stats,
-                void* stream) {
+                const reidmi_search_filter* filter, const float* bound_dist, const int32_t* bound_idx, int64_t ldb,
+                int64_t index_base, int32_t* out_idx, float* out_dist, int64_t ldo, void* ws, int64_t ws_bytes,
+                int splits, int cap, int32_t* stats, void* stream) {
     RM_REQUIRE(Q >= 0 && G > 0 && G < 0x7fffffff && D > 0 && ldq >= D && ldg >= D, "search: bad shape");
     RM_REQUIRE(k >= 1 && k <= G, "search: need 1 <= k <= G");
     RM_REQUIRE(k <= SR_K_MAX,
                "search: k > 128 is not fused; use reidmi_distmat_f32 + reidmi_topk_rows_f32 for larger k");
     RM_REQUIRE(out_idx != nullptr && ldo >= k, "search: out_idx required, ldo >= k");
-    const int nlab = (q_pids != nullptr) + (q_cams != nullptr) + (g_pids != nullptr) + (g_cams != nullptr);
-    RM_REQUIRE(nlab == 0 || nlab == 4, "search: pass all four label arrays or none");
+    SrFilter flt;
+    RM_TRY(sr_filter_make(q_pids, q_cams, g_pids, g_cams, filter, &flt));
     RM_REQUIRE(bound_dist != nullptr || bound_idx == nullptr, "search: bound_idx needs bound_dist");
     RM_REQUIRE(ldb >= 1, "search: need ldb >= 1");
     RM_REQUIRE(index_base >= 0 && index_base + G <= 0x7fffffff,
@@ -413,14 +425,21 @@ int search_impl(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t 
     float* gg = qq + Q;
     float2* lists = (float2*)((char*)ws + dm_norm_bytes(Q, G));
     RM_TRY(dm_norms(q, Q, ldq, g, G, ldg, D, qq, gg, s));
-    const DmLabels lab{q_pids, q_cams, g_pids, g_cams};
     const SrBound bnd{bound_dist, bound_idx, ldb, index_base};
+    const SrLabels lab{flt.qp, flt.qc, flt.gp, flt.gc};
     const dim3 grid((unsigned)(p.bands * p.S));
-    RM_BOOL_SWITCH(dm2_ok(q, ldq, g, ldg, D), PIPE,
-                   RM_BOOL_SWITCH(nlab != 0, LABELS,
-                                  hipLaunchKernelGGL((search_f32_kernel<PIPE, LABELS>), grid, dim3(256), 0, s, q, g,
-                                                     qq, gg, Q, G, D, ldq, ldg, k, lab, bnd, p.range_len, p.cap,
-                                                     lists, stats)));
+    auto arg = [&](auto filter) {
+        if constexpr (decltype(filter)::value) return flt; else return lab;
+    };
+    // no clause present: the instantiations, and so the kernels, of the search without a filter
+    RM_BOOL_SWITCH(
+        dm2_ok(q, ldq, g, ldg, D), PIPE,
+        RM_BOOL_SWITCH(flt.qp != nullptr, LABELS,
+                       RM_BOOL_SWITCH(sr_has_clauses(flt), FILTER,
+                                      hipLaunchKernelGGL((search_f32_kernel<PIPE, LABELS, FILTER>), grid, dim3(256), 0,
+                                                         s, q, g, qq, gg, Q, G, D, ldq, ldg, k,
+                                                         arg(std::bool_constant<FILTER>{}), bnd, p.range_len,
+                                                         p.cap, lists, stats))));
     RM_LAUNCHED();
     hipLaunchKernelGGL(search_merge_kernel, dim3((unsigned)Q), dim3(256), 0, s, (const float2*)lists, p.bands,
                        (int)p.S, p.cap, k, out_idx, out_dist, ldo);
@@ -446,8 +465,8 @@ REIDMI_API int reidmi_search_f32(const float* q, int64_t Q, int64_t ldq, const f
                                  int64_t D, int k, const int64_t* q_pids, const int64_t* q_cams,
                                  const int64_t* g_pids, const int64_t* g_cams, int32_t* out_idx, float* out_dist,
                                  int64_t ldo, void* ws, int64_t ws_bytes, void* stream) {
-    return search_impl(q, Q, ldq, g, G, ldg, D, k, q_pids, q_cams, g_pids, g_cams, nullptr, nullptr, 1, 0, out_idx,
-                       out_dist, ldo, ws, ws_bytes, 0, 0, nullptr, stream);
+    return search_impl(q, Q, ldq, g, G, ldg, D, k, q_pids, q_cams, g_pids, g_cams, nullptr, nullptr, nullptr, 1, 0,
+                       out_idx, out_dist, ldo, ws, ws_bytes, 0, 0, nullptr, stream);
 }
 
 REIDMI_API int reidmi_search_bounded_f32(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G,
@@ -455,7 +474,17 @@ REIDMI_API int reidmi_search_bounded_f32(const float* q, int64_t Q, int64_t ldq,
                                          const int64_t* g_pids, const int64_t* g_cams, const float* bound_dist,
                                          const int32_t* bound_idx, int64_t ldb, int64_t index_base, int32_t* out_idx,
                                          float* out_dist, int64_t ldo, void* ws, int64_t ws_bytes, void* stream) {
-    return search_impl(q, Q, ldq, g, G, ldg, D, k, q_pids, q_cams, g_pids, g_cams, bound_dist, bound_idx, ldb,
+    return search_impl(q, Q, ldq, g, G, ldg, D, k, q_pids, q_cams, g_pids, g_cams, nullptr, bound_dist, bound_idx,
+                       ldb, index_base, out_idx, out_dist, ldo, ws, ws_bytes, 0, 0, nullptr, stream);
+}
+
+REIDMI_API int reidmi_search_filtered_f32(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G,
+                                          int64_t ldg, int64_t D, int k, const int64_t* q_pids, const int64_t* q_cams,
+                                          const int64_t* g_pids, const int64_t* g_cams,
+                                          const reidmi_search_filter* flt, const float* bound_dist,
+                                          const int32_t* bound_idx, int64_t ldb, int64_t index_base, int32_t* out_idx,
+                                          float* out_dist, int64_t ldo, void* ws, int64_t ws_bytes, void* stream) {
+    return search_impl(q, Q, ldq, g, G, ldg, D, k, q_pids, q_cams, g_pids, g_cams, flt, bound_dist, bound_idx, ldb,
                        index_base, out_idx, out_dist, ldo, ws, ws_bytes, 0, 0, nullptr, stream);
 }
 
@@ -478,8 +507,8 @@ REIDMI_API int reidmi_search_f32_ex(const float* q, int64_t Q, int64_t ldq, cons
                                     const int64_t* g_pids, const int64_t* g_cams, int32_t* out_idx, float* out_dist,
                                     int64_t ldo, void* ws, int64_t ws_bytes, int splits, int cap, int32_t* stats,
                                     void* stream) {
-    return search_impl(q, Q, ldq, g, G, ldg, D, k, q_pids, q_cams, g_pids, g_cams, nullptr, nullptr, 1, 0, out_idx,
-                       out_dist, ldo, ws, ws_bytes, splits, cap, stats, stream);
+    return search_impl(q, Q, ldq, g, G, ldg, D, k, q_pids, q_cams, g_pids, g_cams, nullptr, nullptr, nullptr, 1, 0,
+                       out_idx, out_dist, ldo, ws, ws_bytes, splits, cap, stats, stream);
 }
 
 REIDMI_API int reidmi_search_bounded_f32_ex(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G,
@@ -489,7 +518,19 @@ REIDMI_API int reidmi_search_bounded_f32_ex(const float* q, int64_t Q, int64_t l
                                             int64_t index_base, int32_t* out_idx, float* out_dist, int64_t ldo,
                                             void* ws, int64_t ws_bytes, int splits, int cap, int32_t* stats,
                                             void* stream) {
-    return search_impl(q, Q, ldq, g, G, ldg, D, k, q_pids, q_cams, g_pids, g_cams, bound_dist, bound_idx, ldb,
+    return search_impl(q, Q, ldq, g, G, ldg, D, k, q_pids, q_cams, g_pids, g_cams, nullptr, bound_dist, bound_idx,
+                       ldb, index_base, out_idx, out_dist, ldo, ws, ws_bytes, splits, cap, stats, stream);
+}
+
+// reidmi_search_filtered_f32 with the same forced splits, capacity and counters.
+REIDMI_API int reidmi_search_filtered_f32_ex(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G,
+                                             int64_t ldg, int64_t D, int k, const int64_t* q_pids,
+                                             const int64_t* q_cams, const int64_t* g_pids, const int64_t* g_cams,
+                                             const reidmi_search_filter* flt, const float* bound_dist,
+                                             const int32_t* bound_idx, int64_t ldb, int64_t index_base,
+                                             int32_t* out_idx, float* out_dist, int64_t ldo, void* ws,
+                                             int64_t ws_bytes, int splits, int cap, int32_t* stats, void* stream) {
+    return search_impl(q, Q, ldq, g, G, ldg, D, k, q_pids, q_cams, g_pids, g_cams, flt, bound_dist, bound_idx, ldb,
                        index_base, out_idx, out_dist, ldo, ws, ws_bytes, splits, cap, stats, stream);
 }
 #endif

@@ -10,15 +10,21 @@
 //   (d) the exact distances of the candidates, the k smallest    sp_select_kernel
 //
 // Why the lists are the exact search's.  The exact distance d_ij (the distance kernel's bits) lies
-// in [fl(hi_ij - w_i), hi_ij] (rr_width).  (b): U = the k-th smallest hi among the sample items the
-// label rule leaves; those k items have d <= U, so each of the k nearest admissible items has
-// d <= U, and d <= the bound's distance because it is admissible: d <= T = min(U, bound), hence
-// fl(hi - w) <= T and the pair survives (c).  (d) repeats the argument on the survivors (the k-th
-// smallest hi of those the label rule leaves, capped by T), computes the exact distance of what is
-// left, applies reidmi_search_bounded_f32's admissibility on the exact key and selects by the
-// unique key (d, j): the order in which the epilogue's atomics appended the survivors cannot show.
+// in [fl(hi_ij - w_i), hi_ij] (rr_width).  "Admitted" is admit.h's sr_admit: the label rule and
+// the filter's clauses, one definition for this file and the exact search.  (b): U = the k-th
+// smallest hi among the admitted sample items; those k items have d <= U, so each of the k nearest
+// admissible items (admitted, and under the bound) has d <= U, and d <= the bound's distance because
+// it is admissible: d <= T = min(U, bound), hence fl(hi - w) <= T and the pair survives (c), which
+// knows no clause: it keeps admitted and non-admitted pairs alike.  (d) repeats the argument on the
+// survivors (the k-th smallest hi of the admitted ones, capped by T), computes the exact distance of
+// what is left, applies reidmi_search_bounded_f32's bound on the exact key and selects by the unique
+// key (d, j): the order in which the epilogue's atomics appended the survivors cannot show.
+// A selective filter leaves few admitted sample items, so U is loose (fewer than k of them: +inf)
+// and the survivor lists, which hold non-admitted pairs too, overflow: such rows go to the exact
+// filtered search.  Correct, and slower than calling the exact search at once.
 // A row whose list overflows (more than RR_SV_CAP survivors), or that holds a non-finite bound, is
 // marked in need[] and left to the exact search; so is every row when a feature is outside fp16's range.
+#include "admit.h"
 #include "backend.h"
 #include "prefilter.h"
 #include "select.h"
@@ -28,9 +34,6 @@ namespace reidmi {
 constexpr int SP_K_MAX = 128;               // reidmi_search_f32's
 constexpr int64_t SP_PASS_BYTES = 1ll << 30;  // per-pass state (sample bounds + survivor lists) aimed at
 
-struct SpLabels {
-    const int64_t *qp, *qc, *gp, *gc;
-};
 struct SpBound {  // reidmi_search_bounded_f32's (search.hip SrBound)
     const float* dist;
     const int32_t* idx;
@@ -57,7 +60,7 @@ __global__ void sp_sqrt_kernel(const float* __restrict__ x, int64_t n, float* __
 }
 
 // (b) One workgroup per row r of the pass (query row0 + r): U = the K-th smallest hi among the
-// sample items (position t = gallery item t S) that the label rule leaves, T = min(U, the row's
+// sample items (position t = gallery item t S) that are admitted (sr_admit), T = min(U, the row's
 // bound distance) (a NaN or -inf bound: -inf, nothing survives), and the survivor epilogue's
 // row record (s, n, hi_max(T), +inf): with lb = +inf the epilogue's test keeps exactly hi <= hi_max.
 // Fewer than K such sample items and no finite bound: T = +inf, everything survives (the row
@@ -66,7 +69,7 @@ __global__ __launch_bounds__(256) void sp_threshold_kernel(const float* __restri
                                                            const float* __restrict__ qq,
                                                            const float* __restrict__ qn,
                                                            const SpState* __restrict__ st, int64_t row0, int K,
-                                                           float c_rel, float c_abs, float c_d, SpLabels lab,
+                                                           float c_rel, float c_abs, float c_d, SrFilter flt,
                                                            SpBound bnd, float4* __restrict__ meta,
                                                            float* __restrict__ wrow, float* __restrict__ trow,
                                                            int32_t* __restrict__ cnt, int cap) {
@@ -76,11 +79,11 @@ __global__ __launch_bounds__(256) void sp_threshold_kernel(const float* __restri
     int bad = 0;
     for (int64_t t = threadIdx.x; t < ns; t += blockDim.x) bad |= !(fabsf(row[t]) < __builtin_inff());
     bad = __syncthreads_or(bad);
-    if (lab.qp != nullptr) {
-        const int64_t qp = lab.qp[i], qc = lab.qc[i];
+    const bool labels = flt.qp != nullptr, clauses = sr_has_clauses(flt);
+    if (labels || clauses) {
+        const SrRow qside = sr_row(flt, labels, clauses, i);
         topk_row_dev([&](int64_t t) { return row[t]; }, ns, K, L, [&](float, int t) {
-            const int64_t j = (int64_t)t * S;
-            return !(lab.gp[j] == qp && lab.gc[j] == qc);  // evaluate.py:46-48
+            return sr_admit(flt, labels, clauses, qside, sr_item(flt, labels, clauses, (int64_t)t * S));
         });
     } else {
         topk_row_dev([&](int64_t t) { return row[t]; }, ns, K, L);
@@ -114,7 +117,7 @@ __global__ __launch_bounds__(256) void sp_select_kernel(const int32_t* __restric
                                                         const float* __restrict__ g, int64_t ldg, int D, bool vec,
                                                         const float* __restrict__ qq,
                                                         const float* __restrict__ gg, int64_t row0, int64_t G,
-                                                        int K, SpLabels lab, SpBound bnd, SpState* __restrict__ st,
+                                                        int K, SrFilter flt, SpBound bnd, SpState* __restrict__ st,
                                                         int32_t* __restrict__ out_idx, float* __restrict__ out_dist,
                                                         int64_t ldo, int32_t* __restrict__ need) {
     __shared__ float sv[RR_SV_CAP];
@@ -131,8 +134,8 @@ __global__ __launch_bounds__(256) void sp_select_kernel(const int32_t* __restric
         return;
     }
     const int2* lr = list + r * (int64_t)cap;
-    const bool labels = lab.qp != nullptr;
-    const int64_t qp = labels ? lab.qp[i] : 0, qc = labels ? lab.qc[i] : 0;
+    const bool labels = flt.qp != nullptr, clauses = sr_has_clauses(flt);
+    const SrRow qside = sr_row(flt, labels, clauses, i);
     const int P = pow2_ceil(n < 2 ? 2 : n);
     if (threadIdx.x == 0) { s_rm = 0; s_nc = 0; }
     __syncthreads();
@@ -145,7 +148,8 @@ __global__ __launch_bounds__(256) void sp_select_kernel(const int32_t* __restric
             h = __builtin_bit_cast(float, e.y);
             j = e.x;
             bad |= !(fabsf(h) < __builtin_inff());
-            if (labels && lab.gp[j] == qp && lab.gc[j] == qc) {  // the label rule: never a candidate
+            if ((labels || clauses) &&
+                !sr_admit(flt, labels, clauses, qside, sr_item(flt, labels, clauses, j))) {  // never a candidate
                 h = __builtin_inff();
                 j = 0x7fffffff;
                 removed++;
@@ -300,21 +304,20 @@ REIDMI_API int64_t reidmi_search_prefiltered_workspace_bytes(int64_t Q, int64_t 
     return sp_plan(Q, G, D, k, sample_stride, &p) ? p.bytes : -1;
 }
 
-REIDMI_API int reidmi_search_prefiltered_f32(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G,
-                                             int64_t ldg, int64_t D, int k, const int64_t* q_pids,
-                                             const int64_t* q_cams, const int64_t* g_pids, const int64_t* g_cams,
-                                             const float* bound_dist, const int32_t* bound_idx, int64_t ldb,
-                                             int64_t index_base, int32_t* out_idx, float* out_dist, int64_t ldo,
-                                             int sample_stride, int32_t* need, int32_t* stats, void* ws,
-                                             int64_t ws_bytes, void* stream) {
+static int search_prefiltered_impl(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G, int64_t ldg,
+                                   int64_t D, int k, const int64_t* q_pids, const int64_t* q_cams,
+                                   const int64_t* g_pids, const int64_t* g_cams, const reidmi_search_filter* filter,
+                                   const float* bound_dist, const int32_t* bound_idx, int64_t ldb, int64_t index_base,
+                                   int32_t* out_idx, float* out_dist, int64_t ldo, int sample_stride, int32_t* need,
+                                   int32_t* stats, void* ws, int64_t ws_bytes, void* stream) {
     // reidmi_search_bounded_f32's refusals (search.hip search_impl), then this call's own
     RM_REQUIRE(Q >= 0 && G > 0 && G < 0x7fffffff && D > 0 && ldq >= D && ldg >= D, "search: bad shape");
     RM_REQUIRE(k >= 1 && k <= G, "search: need 1 <= k <= G");
     RM_REQUIRE(k <= SP_K_MAX,
                "search: k > 128 is not fused; use reidmi_distmat_f32 + reidmi_topk_rows_f32 for larger k");
     RM_REQUIRE(out_idx != nullptr && ldo >= k, "search: out_idx required, ldo >= k");
-    const int nlab = (q_pids != nullptr) + (q_cams != nullptr) + (g_pids != nullptr) + (g_cams != nullptr);
-    RM_REQUIRE(nlab == 0 || nlab == 4, "search: pass all four label arrays or none");
+    SrFilter flt;
+    RM_TRY(sr_filter_make(q_pids, q_cams, g_pids, g_cams, filter, &flt));
     RM_REQUIRE(bound_dist != nullptr || bound_idx == nullptr, "search: bound_idx needs bound_dist");
     RM_REQUIRE(ldb >= 1, "search: need ldb >= 1");
     RM_REQUIRE(index_base >= 0 && index_base + G <= 0x7fffffff,
@@ -361,7 +364,6 @@ REIDMI_API int reidmi_search_prefiltered_f32(const float* q, int64_t Q, int64_t 
 
     float c[3];
     rank_select_consts((int)D, c);
-    const SpLabels lab{q_pids, q_cams, g_pids, g_cams};
     const SpBound bnd{bound_dist, bound_idx, ldb, index_base};
     const bool vec = (((uintptr_t)q | (uintptr_t)g) & 15) == 0 && (ldq & 3) == 0 && (ldg & 3) == 0;
     int tm_listed = -1;
@@ -376,12 +378,12 @@ REIDMI_API int reidmi_search_prefiltered_f32(const float* q, int64_t Q, int64_t 
         RM_TRY(rr_hi_sample_launch(q16 + a * p.Dp, p.Dp, g16, (int64_t)p.S * p.Dp, qq, qn, a, nb, sqn_s, nrm_s, p.ns, D,
                                    hs, s));
         hipLaunchKernelGGL(sp_threshold_kernel, dim3((unsigned)nb), dim3(256), 0, s, hs, p.ns, p.S, qq, qn, st, a, k,
-                           c[0], c[1], c[2], lab, bnd, meta, wrow, trow, cnt, RR_SV_CAP);
+                           c[0], c[1], c[2], flt, bnd, meta, wrow, trow, cnt, RR_SV_CAP);
         RM_LAUNCHED();
         RM_TRY(rr_survivors_launch(q16 + a * p.Dp, g16, p.Dp, p.Gp, G, D, nb, meta, colrec, tiles, (int64_t)tm * T,
                                    false, cnt, list, RR_SV_CAP, s));
         hipLaunchKernelGGL(sp_select_kernel, dim3((unsigned)nb), dim3(256), 0, s, cnt, list, RR_SV_CAP, wrow, trow, q,
-                           ldq, g, ldg, (int)D, vec, qq, gg, a, G, k, lab, bnd, st, out_idx, out_dist, ldo, need);
+                           ldq, g, ldg, (int)D, vec, qq, gg, a, G, k, flt, bnd, st, out_idx, out_dist, ldo, need);
         RM_LAUNCHED();
     }
     if (stats != nullptr) {
@@ -389,4 +391,27 @@ REIDMI_API int reidmi_search_prefiltered_f32(const float* q, int64_t Q, int64_t 
         RM_LAUNCHED();
     }
     return OK;
+}
+
+REIDMI_API int reidmi_search_prefiltered_f32(const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G,
+                                             int64_t ldg, int64_t D, int k, const int64_t* q_pids,
+                                             const int64_t* q_cams, const int64_t* g_pids, const int64_t* g_cams,
+                                             const float* bound_dist, const int32_t* bound_idx, int64_t ldb,
+                                             int64_t index_base, int32_t* out_idx, float* out_dist, int64_t ldo,
+                                             int sample_stride, int32_t* need, int32_t* stats, void* ws,
+                                             int64_t ws_bytes, void* stream) {
+    return search_prefiltered_impl(q, Q, ldq, g, G, ldg, D, k, q_pids, q_cams, g_pids, g_cams, nullptr, bound_dist,
+                                   bound_idx, ldb, index_base, out_idx, out_dist, ldo, sample_stride, need, stats, ws,
+                                   ws_bytes, stream);
+}
+
+REIDMI_API int reidmi_search_prefiltered_filtered_f32(
+    const float* q, int64_t Q, int64_t ldq, const float* g, int64_t G, int64_t ldg, int64_t D, int k,
+    const int64_t* q_pids, const int64_t* q_cams, const int64_t* g_pids, const int64_t* g_cams,
+    const reidmi_search_filter* flt, const float* bound_dist, const int32_t* bound_idx, int64_t ldb, int64_t index_base,
+    int32_t* out_idx, float* out_dist, int64_t ldo, int sample_stride, int32_t* need, int32_t* stats, void* ws,
+    int64_t ws_bytes, void* stream) {
+    return search_prefiltered_impl(q, Q, ldq, g, G, ldg, D, k, q_pids, q_cams, g_pids, g_cams, flt, bound_dist,
+                                   bound_idx, ldb, index_base, out_idx, out_dist, ldo, sample_stride, need, stats, ws,
+                                   ws_bytes, stream);
 }

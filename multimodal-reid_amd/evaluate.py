@@ -116,8 +116,185 @@ def _max_dist_rows(what, max_dist, Q):
     return t.to(torch.float32)
 
 
+# ------------------------------------------------------------- filtered search
+# Which gallery items a query may match at all (reidmi_search_filter, include/reidmi.h).  Item j is
+# admitted for query i iff every clause that is present holds:
+#   valid        ItemAttrs.valid[j] != 0
+#   camera mask  0 <= ItemAttrs.camids[j] < 64 and bit camids[j] of QueryFilter.cam_mask[i] is set
+#   time window  time_range[i][0] <= ItemAttrs.times[j] <= time_range[i][1]
+#   group        ItemAttrs.groups[j] != QueryFilter.groups[i]
+# next to the label rule of the four label arrays (not (same pid and same camera)).  The kernels test
+# the clauses where they test the label rule (csrc/admit.h): nothing is fetched and filtered later.
+class ItemAttrs:
+    """The gallery side of a filtered search: one entry per gallery row, each array optional.
+    valid (bool / uint8): 0 withdraws the item.  camids, times, groups (integers): the item's camera
+    for QueryFilter.cam_mask (0 .. 63), its time stamp for time_range, its group (a tracklet, a
+    sequence of inference()'s seqs) for QueryFilter.groups.  Host arrays or device tensors."""
+
+    def __init__(self, valid=None, camids=None, times=None, groups=None):
+        self.valid, self.camids, self.times, self.groups = valid, camids, times, groups
+
+    def __getitem__(self, rows):
+        """The attributes of a block of gallery rows (a slice or an index array)."""
+        return ItemAttrs(*(None if a is None else a[rows] for a in (self.valid, self.camids, self.times, self.groups)))
+
+
+class QueryFilter:
+    """The query side of a filtered search.  cam_mask: one int64 per query read as 64 bits, bit c set
+    = camera c may match (cam_mask(), cross_camera_mask()).  time_range: [Q][2] integers (lo, hi), or
+    one (lo, hi) pair for every query; both ends are inside the window.  groups: one integer per
+    query, items of that group are left out (the query's own tracklet)."""
+
+    def __init__(self, cam_mask=None, time_range=None, groups=None):
+        self.cam_mask, self.time_range, self.groups = cam_mask, time_range, groups
+
+
+def cam_mask(allowed):
+    """The int64 whose bit c is set for every camera id c in ``allowed`` (0 .. 63)."""
+    m = 0
+    for c in allowed:
+        c = int(c)
+        if not 0 <= c < 64:
+            raise _lib.ReidmiError(f"cam_mask: camera ids must be in [0, 64), not {c}")
+        m |= 1 << c
+    return np.uint64(m).astype(np.int64)
+
+
+def cross_camera_mask(q_camids):
+    """int64 [Q]: for every query every bit but its own camera's (cross-camera-only matching: items
+    of the query's camera are dropped whatever their pid)."""
+    c = np.asarray(q_camids.cpu() if isinstance(q_camids, torch.Tensor) else q_camids)
+    if c.ndim != 1 or c.dtype.kind not in "iu":
+        raise _lib.ReidmiError("cross_camera_mask: q_camids must be one integer per query")
+    if c.size and (c.min() < 0 or c.max() >= 64):
+        raise _lib.ReidmiError("cross_camera_mask: camera ids must be in [0, 64)")
+    return (~(np.uint64(1) << c.astype(np.uint64))).astype(np.int64)
+
+
+_INT_DTYPES = (torch.int8, torch.int16, torch.int32, torch.int64, torch.uint8)
+
+
+def _filter_array(what, name, x, n, kinds="iu"):
+    """x as a torch tensor of shape [n] and an integer (or, for valid, bool) dtype, where it is."""
+    if not isinstance(x, torch.Tensor):
+        try:
+            a = np.asarray(x)
+            if a.dtype.kind not in kinds:
+                raise TypeError
+            if a.dtype == np.uint64:
+                a = a.astype(np.int64)  # the same 64 bits
+            x = torch.from_numpy(np.ascontiguousarray(a))
+        except (TypeError, ValueError):
+            raise _lib.ReidmiError(f"{what}: {name} must be an integer array, one entry per row") from None
+    allowed = (torch.bool, torch.uint8) if kinds == "biu" else _INT_DTYPES
+    if x.dtype not in allowed:
+        want = "bool or uint8" if kinds == "biu" else "an integer dtype"
+        raise _lib.ReidmiError(f"{what}: {name} must have {want}, not {x.dtype}")
+    if tuple(x.shape) != (n,):
+        raise _lib.ReidmiError(f"{what}: {name} must have shape [{n}], not {list(x.shape)}")
+    return x.detach()
+
+
+class _Filter:
+    """A checked filter: tensors (host or device) until to(), then device tensors the C struct points to."""
+    NAMES = ("g_valid", "g_cam", "q_cam_mask", "g_time", "q_time_lo", "q_time_hi", "g_group", "q_group")
+
+    def __init__(self, **kw):
+        for n in self.NAMES:
+            setattr(self, n, kw.get(n))
+
+    def to(self, dev):
+        f = _Filter()
+        for n in self.NAMES:
+            t = getattr(self, n)
+            if t is not None:
+                t = t.to(device=dev, dtype=torch.uint8 if n == "g_valid" else torch.int64).contiguous()
+            setattr(f, n, t)
+        return f
+
+    def rows(self, rows):
+        """The filter of a subset of the queries."""
+        f = _Filter(**{n: getattr(self, n) for n in self.NAMES})
+        for n in self.NAMES:
+            if n.startswith("q_") and getattr(self, n) is not None:
+                setattr(f, n, getattr(self, n)[rows].contiguous())
+        return f
+
+    def struct(self):
+        s = _lib.structs("reidmi_filter.h")["reidmi_search_filter"]()
+        for n in self.NAMES:
+            t = getattr(self, n)
+            setattr(s, n, None if t is None else t.data_ptr())
+        return s
+
+
+def _check_query_filter(what, q_filter, Q):
+    """QueryFilter -> {q_cam_mask, q_time_lo, q_time_hi, q_group} tensors; host code only."""
+    if q_filter is None:
+        return {}
+    if not isinstance(q_filter, QueryFilter):
+        raise _lib.ReidmiError(f"{what}: q_filter must be an evaluate.QueryFilter")
+    out = {}
+    if q_filter.cam_mask is not None:
+        out["q_cam_mask"] = _filter_array(what, "q_filter.cam_mask", q_filter.cam_mask, Q)
+    if q_filter.time_range is not None:
+        tr = q_filter.time_range
+        if not isinstance(tr, torch.Tensor):
+            try:
+                a = np.asarray(tr)
+                if a.dtype.kind not in "iu":
+                    raise TypeError
+                tr = torch.from_numpy(np.ascontiguousarray(a.astype(np.int64)))
+            except (TypeError, ValueError):
+                raise _lib.ReidmiError(f"{what}: q_filter.time_range must hold integers") from None
+        if tr.dtype not in _INT_DTYPES:
+            raise _lib.ReidmiError(f"{what}: q_filter.time_range must have an integer dtype, not {tr.dtype}")
+        if tuple(tr.shape) == (2,):
+            tr = tr.reshape(1, 2).expand(Q, 2)
+        if tuple(tr.shape) != (Q, 2):
+            raise _lib.ReidmiError(f"{what}: q_filter.time_range must be one (lo, hi) pair or have shape [{Q}, 2], "
+                                   f"not {list(tr.shape)}")
+        out["q_time_lo"], out["q_time_hi"] = tr[:, 0].detach(), tr[:, 1].detach()
+    if q_filter.groups is not None:
+        out["q_group"] = _filter_array(what, "q_filter.groups", q_filter.groups, Q)
+    return out
+
+
+_CLAUSES = (("camera mask", "g_attrs.camids", "g_cam", "q_filter.cam_mask", "q_cam_mask"),
+            ("time window", "g_attrs.times", "g_time", "q_filter.time_range", "q_time_lo"),
+            ("group", "g_attrs.groups", "g_group", "q_filter.groups", "q_group"))
+
+
+def _check_filter(what, g_attrs, G, qside):
+    """ItemAttrs of G rows and a checked query side -> _Filter, or None when neither holds anything.
+    Raises for a clause with one side only and, with a camera mask, for a camera id outside [0, 64):
+    on the host for a host array, one device reduction and one synchronisation for a device tensor."""
+    if g_attrs is None and not qside:
+        return None
+    if g_attrs is not None and not isinstance(g_attrs, ItemAttrs):
+        raise _lib.ReidmiError(f"{what}: g_attrs must be an evaluate.ItemAttrs")
+    g = {}
+    if g_attrs is not None:
+        if g_attrs.valid is not None:
+            g["g_valid"] = _filter_array(what, "g_attrs.valid", g_attrs.valid, G, "biu")
+        for name, key in (("camids", "g_cam"), ("times", "g_time"), ("groups", "g_group")):
+            if getattr(g_attrs, name) is not None:
+                g[key] = _filter_array(what, "g_attrs." + name, getattr(g_attrs, name), G)
+    for clause, gname, gkey, qname, qkey in _CLAUSES:
+        if (gkey in g) != (qkey in qside):
+            have, miss = (gname, qname) if gkey in g else (qname, gname)
+            raise _lib.ReidmiError(f"{what}: the {clause} clause has {have} but no {miss}")
+    if "g_cam" in g and G:
+        c = g["g_cam"]
+        if bool(((c < 0) | (c >= 64)).any()):
+            raise _lib.ReidmiError(f"{what}: g_attrs.camids must be in [0, 64) when a camera mask is given")
+    if not g and not qside:
+        return None
+    return _Filter(**g, **qside)
+
+
 def search_device(qf, gf, k, q_pids=None, q_camids=None, g_pids=None, g_camids=None, with_dist=True, max_dist=None,
-                  prefilter=False, return_stats=False, _sample_stride=0):
+                  prefilter=False, return_stats=False, _sample_stride=0, g_attrs=None, q_filter=None):
     """The k nearest gallery rows of every query row (reidmi_search_f32: the selection runs in the
     distance kernel's epilogue, no (Q,G) matrix): (idx int32 [Q][k], dist fp32 [Q][k] or None) on the
     GPU, bit for bit euclidean_distance_device + topk_rows_device.  With the four label arrays, gallery
@@ -136,9 +313,22 @@ def search_device(qf, gf, k, q_pids=None, q_camids=None, g_pids=None, g_camids=N
     such rows there are is this path's one synchronisation with the GPU.  Faster on large galleries,
     slower on small ones.
     return_stats: also return a dict: applied (the pre-filtered call ran), need_rows (rows it left to
-    the exact search), max_survivors, rescored (exact distances it computed), range_failed."""
+    the exact search), max_survivors, rescored (exact distances it computed), range_failed.
+    g_attrs (ItemAttrs) / q_filter (QueryFilter): the filtered search (reidmi_search_filtered_f32).
+    Only admitted items are ranked: the clauses of the table above ItemAttrs, tested in the kernel
+    next to the label rule, with or without labels, max_dist and prefilter; a query with fewer than
+    k admitted items gets a short row, one with none an all-padded row.  A clause needs both its
+    sides (valid has the gallery side only); shapes, dtypes and the pairing are checked before
+    anything touches the GPU, and with a camera mask the gallery's camera ids must lie in [0, 64):
+    for a device tensor that check costs one device reduction and one synchronisation, for a host
+    array nothing.  With prefilter, the rows it marks go through the filtered exact search with the
+    same filter; a selective filter starves the pre-filter's 1/16 sample and overflows its survivor
+    lists, so most rows fall back (need_rows in return_stats) and the exact filtered search alone is
+    the faster call.  Both None: the unfiltered kernels, as before."""
     tau = _max_dist_rows("search", max_dist, qf.shape[0])
+    flt = _check_filter("search", g_attrs, gf.shape[0], _check_query_filter("search", q_filter, qf.shape[0]))
     qf, gf = _as_dev_f32(qf), _as_dev_f32(gf)
+    flt = None if flt is None else flt.to(qf.device)
     Q, D = qf.shape
     G = gf.shape[0]
     labels = (q_pids, q_camids, g_pids, g_camids)
@@ -152,20 +342,28 @@ def search_device(qf, gf, k, q_pids=None, q_camids=None, g_pids=None, g_camids=N
     bound = None if tau is None else (tau.to(qf.device).contiguous(), None, 1, 0)
     stats = dict(_NO_PREFILTER)
     if prefilter:
-        stats = _search_prefiltered_into(qf, gf, k, (qp, qc, gp, gc), idx, dist, max(k, 1), bound, _sample_stride)
+        stats = _search_prefiltered_into(qf, gf, k, (qp, qc, gp, gc), idx, dist, max(k, 1), bound, _sample_stride,
+                                         flt)
     else:
-        _search_into(qf, gf, k, (qp, qc, gp, gc), idx, dist, max(k, 1), bound)
+        _search_into(qf, gf, k, (qp, qc, gp, gc), idx, dist, max(k, 1), bound, flt)
     return (idx, dist, stats) if return_stats else (idx, dist)
 
 
-def _search_into(qf, gf, k, labels, idx, dist, ldo, bound=None):
+def _search_into(qf, gf, k, labels, idx, dist, ldo, bound=None, flt=None):
     """reidmi_search_f32 of device features (and device labels, or four Nones) into rows of pitch ldo.
     bound: None, or reidmi_search_bounded_f32's (bound_dist, bound_idx or None, ldb, index_base), the
-    first two device tensors (or views) whose element i * ldb belongs to query i."""
+    first two device tensors (or views) whose element i * ldb belongs to query i.  flt: None, or a
+    _Filter on the device (reidmi_search_filtered_f32)."""
     Q, D = qf.shape
     G = gf.shape[0]
     nb = _lib.load().reidmi_search_workspace_bytes(Q, G, D, k)
     ws = torch.empty(max(nb, 16), device=qf.device, dtype=torch.uint8)
+    if flt is not None:
+        bd, bi, ldb, base = (None, None, 1, 0) if bound is None else bound
+        _lib.call("reidmi_search_filtered_f32", _lib.ptr(qf), Q, qf.stride(0), _lib.ptr(gf), G, gf.stride(0), D, k,
+                  *(_lib.ptr(a) for a in labels), ctypes.byref(flt.struct()), _lib.ptr(bd), _lib.ptr(bi), ldb, base,
+                  _lib.ptr(idx), _lib.ptr(dist), ldo, _lib.ptr(ws), nb, _lib.stream())
+        return
     if bound is None:
         _lib.call("reidmi_search_f32", _lib.ptr(qf), Q, qf.stride(0), _lib.ptr(gf), G, gf.stride(0), D, k,
                   *(_lib.ptr(a) for a in labels), _lib.ptr(idx), _lib.ptr(dist), ldo, _lib.ptr(ws), nb, _lib.stream())
@@ -179,7 +377,7 @@ def _search_into(qf, gf, k, labels, idx, dist, ldo, bound=None):
 _NO_PREFILTER = {"applied": False, "need_rows": 0, "max_survivors": 0, "rescored": 0, "range_failed": 0}
 
 
-def _search_prefiltered_into(qf, gf, k, labels, idx, dist, ldo, bound=None, sample_stride=0):
+def _search_prefiltered_into(qf, gf, k, labels, idx, dist, ldo, bound=None, sample_stride=0, flt=None):
     """_search_into through reidmi_search_prefiltered_f32 (same arguments; idx / dist are [Q][>= k]
     tensors of pitch ldo): the exact search where the pre-filter does not apply, else the pre-filtered
     call, then the exact search of the rows it marked in need, scattered back.  Returns search_device's
@@ -188,16 +386,22 @@ def _search_prefiltered_into(qf, gf, k, labels, idx, dist, ldo, bound=None, samp
     G = gf.shape[0]
     L = _lib.load()
     if Q == 0 or not L.reidmi_search_prefilter_applies(Q, G, D, k, sample_stride):
-        _search_into(qf, gf, k, labels, idx, dist, ldo, bound)
+        _search_into(qf, gf, k, labels, idx, dist, ldo, bound, flt)
         return dict(_NO_PREFILTER)
     nb = L.reidmi_search_prefiltered_workspace_bytes(Q, G, D, k, sample_stride)
     ws = torch.empty(nb, device=qf.device, dtype=torch.uint8)
     need = torch.empty(Q, device=qf.device, dtype=torch.int32)
     stats = torch.empty(4, device=qf.device, dtype=torch.int32)
     bd, bi, ldb, base = (None, None, 1, 0) if bound is None else bound
-    _lib.call("reidmi_search_prefiltered_f32", _lib.ptr(qf), Q, qf.stride(0), _lib.ptr(gf), G, gf.stride(0), D, k,
-              *(_lib.ptr(a) for a in labels), _lib.ptr(bd), _lib.ptr(bi), ldb, base, _lib.ptr(idx), _lib.ptr(dist),
-              ldo, sample_stride, _lib.ptr(need), _lib.ptr(stats), _lib.ptr(ws), nb, _lib.stream())
+    if flt is None:
+        _lib.call("reidmi_search_prefiltered_f32", _lib.ptr(qf), Q, qf.stride(0), _lib.ptr(gf), G, gf.stride(0), D, k,
+                  *(_lib.ptr(a) for a in labels), _lib.ptr(bd), _lib.ptr(bi), ldb, base, _lib.ptr(idx), _lib.ptr(dist),
+                  ldo, sample_stride, _lib.ptr(need), _lib.ptr(stats), _lib.ptr(ws), nb, _lib.stream())
+    else:
+        _lib.call("reidmi_search_prefiltered_filtered_f32", _lib.ptr(qf), Q, qf.stride(0), _lib.ptr(gf), G,
+                  gf.stride(0), D, k, *(_lib.ptr(a) for a in labels), ctypes.byref(flt.struct()), _lib.ptr(bd),
+                  _lib.ptr(bi), ldb, base, _lib.ptr(idx), _lib.ptr(dist), ldo, sample_stride, _lib.ptr(need),
+                  _lib.ptr(stats), _lib.ptr(ws), nb, _lib.stream())
     st = stats.tolist()
     if st[0]:
         rows = torch.nonzero(need).squeeze(1)
@@ -207,7 +411,8 @@ def _search_prefiltered_into(qf, gf, k, labels, idx, dist, ldo, bound=None, samp
                                                 1, base)
         sidx = torch.empty((n, k), device=qf.device, dtype=torch.int32)
         sdist = None if dist is None else torch.empty((n, k), device=qf.device, dtype=torch.float32)
-        _search_into(qf[rows].contiguous(), gf, k, sub_lab, sidx, sdist, k, sub_bound)
+        _search_into(qf[rows].contiguous(), gf, k, sub_lab, sidx, sdist, k, sub_bound,
+                     None if flt is None else flt.rows(rows))
         idx[rows, :k] = sidx
         if dist is not None:
             dist[rows, :k] = sdist
@@ -215,9 +420,10 @@ def _search_prefiltered_into(qf, gf, k, labels, idx, dist, ldo, bound=None, samp
 
 
 def search(qf, gf, k, q_pids=None, q_camids=None, g_pids=None, g_camids=None, with_dist=True, max_dist=None,
-           prefilter=False):
+           prefilter=False, g_attrs=None, q_filter=None):
     """search_device, returned as numpy arrays."""
-    idx, dist = search_device(qf, gf, k, q_pids, q_camids, g_pids, g_camids, with_dist, max_dist, prefilter)
+    idx, dist = search_device(qf, gf, k, q_pids, q_camids, g_pids, g_camids, with_dist, max_dist, prefilter,
+                              g_attrs=g_attrs, q_filter=q_filter)
     return idx.cpu().numpy(), (dist.cpu().numpy() if with_dist else None)
 
 
@@ -278,11 +484,17 @@ class SearchAccumulator:
     searched under a bound that admits more than the radius.
     prefilter (default False): every block's search goes through search_device(prefilter=True)'s
     path, the carried bound and the radius as its bound arguments; a block too small for the
-    pre-filter takes the exact search.  The result is the same, bit for bit."""
+    pre-filter takes the exact search.  The result is the same, bit for bit.
+    q_filter (QueryFilter): the filtered search; every add() then brings the block's g_attrs
+    (ItemAttrs) with the gallery side of each of its clauses (g_attrs.valid needs no q_filter), checked
+    as search_device checks them.  Bit for bit search_device(..., g_attrs=, q_filter=) over the
+    concatenation, carry_bound on or off: the carried key is an admitted item's, so it bounds admitted
+    items exactly.  A block in which nothing is admitted adds nothing."""
 
     def __init__(self, qf, k, q_pids=None, q_camids=None, with_dist=True, carry_bound=CARRY_BOUND_DEFAULT,
-                 max_dist=None, prefilter=False, _sample_stride=0):
+                 max_dist=None, prefilter=False, _sample_stride=0, q_filter=None):
         self.prefilter, self._sample_stride = bool(prefilter), int(_sample_stride)
+        self._qside = _check_query_filter("SearchAccumulator", q_filter, qf.shape[0])
         if not isinstance(carry_bound, (bool, np.bool_)):
             raise _lib.ReidmiError("SearchAccumulator: carry_bound must be True or False")
         tau = _max_dist_rows("SearchAccumulator", max_dist, qf.shape[0])
@@ -302,14 +514,16 @@ class SearchAccumulator:
         self._carried = 0
         self.count = 0  # gallery items added so far
 
-    def add(self, gf_block, g_pids=None, g_camids=None):
+    def add(self, gf_block, g_pids=None, g_camids=None, g_attrs=None):
         if _labels_given("SearchAccumulator.add", g_pids, g_camids) != self.labels:
             raise _lib.ReidmiError("SearchAccumulator.add: gallery labels go with query labels: every block has "
                                    "them or none has")
         rows = int(gf_block.shape[0])
+        flt = _check_filter("SearchAccumulator.add", g_attrs, rows, self._qside)
         if rows == 0:
             return
         gf = _as_dev_f32(gf_block)
+        flt = None if flt is None else flt.to(gf.device)
         lab = (self.qp, self.qc, _as_dev_i64(g_pids), _as_dev_i64(g_camids)) if self.labels else (None,) * 4
         if self.labels and (lab[2].numel() != rows or lab[3].numel() != rows):
             raise _lib.ReidmiError("SearchAccumulator.add: one label per gallery row")
@@ -322,9 +536,9 @@ class SearchAccumulator:
             self._dist[slot].fill_(float("inf"))
         if self.prefilter:
             _search_prefiltered_into(self.qf, gf, kb, lab, self._idx[slot], self._dist[slot], self.k, self._bound(),
-                                     self._sample_stride)
+                                     self._sample_stride, flt)
         else:
-            _search_into(self.qf, gf, kb, lab, self._idx[slot], self._dist[slot], self.k, self._bound())
+            _search_into(self.qf, gf, kb, lab, self._idx[slot], self._dist[slot], self.k, self._bound(), flt)
         if self.count:
             c = self._carried
             lo = min(c, 1)  # lists lo and lo + 1
@@ -357,20 +571,22 @@ class SearchAccumulator:
 
 
 def search_blocks_device(qf, blocks, k, q_pids=None, q_camids=None, with_dist=True,
-                         carry_bound=CARRY_BOUND_DEFAULT, max_dist=None, prefilter=False):
+                         carry_bound=CARRY_BOUND_DEFAULT, max_dist=None, prefilter=False, q_filter=None):
     """SearchAccumulator over ``blocks``: an iterable of feature blocks or, with query labels, of
-    (features, g_pids, g_camids) tuples.  Bit for bit search_device over their concatenation (with
-    the same max_dist), whatever carry_bound and prefilter are."""
-    acc = SearchAccumulator(qf, k, q_pids, q_camids, with_dist, carry_bound, max_dist, prefilter)
+    (features, g_pids, g_camids) tuples; with a filter, of (features, g_pids, g_camids, g_attrs)
+    tuples (the labels None without query labels).  Bit for bit search_device over their
+    concatenation (with the same max_dist and filter), whatever carry_bound and prefilter are."""
+    acc = SearchAccumulator(qf, k, q_pids, q_camids, with_dist, carry_bound, max_dist, prefilter, q_filter=q_filter)
     for b in blocks:
         acc.add(*b) if isinstance(b, (tuple, list)) else acc.add(b)
     return acc.result()
 
 
 def search_blocks(qf, blocks, k, q_pids=None, q_camids=None, with_dist=True, carry_bound=CARRY_BOUND_DEFAULT,
-                  max_dist=None, prefilter=False):
+                  max_dist=None, prefilter=False, q_filter=None):
     """search_blocks_device, returned as numpy arrays."""
-    idx, dist = search_blocks_device(qf, blocks, k, q_pids, q_camids, with_dist, carry_bound, max_dist, prefilter)
+    idx, dist = search_blocks_device(qf, blocks, k, q_pids, q_camids, with_dist, carry_bound, max_dist, prefilter,
+                                     q_filter)
     return idx.cpu().numpy(), (dist.cpu().numpy() if with_dist else None)
 
 
@@ -1274,7 +1490,7 @@ class R1_mAP_eval():
         self._print(cmc, mAP)
         return cmc, mAP
 
-    def rank_lists(self, k=10, remove_same_cam=True, prefilter=False):
+    def rank_lists(self, k=10, remove_same_cam=True, prefilter=False, g_attrs=None, q_filter=None):
         """The ranked lists behind compute()'s scores (SURVEY.md §8e "top-max_rank rank lists for
         output"): numpy (idx int32 [num_query][k], dist fp32 [num_query][k]) of the query rows against
         the gallery rows, features normalised as compute() does, nearest first, ties by gallery index;
@@ -1290,9 +1506,16 @@ class R1_mAP_eval():
         lists, not features); the re-ranked ones gather features and labels as compute() does (the
         k-reciprocal stages need the whole gallery) and shard the rows (re_ranking_search(sharded=True)).
         prefilter: the single-process Euclidean lists through search(prefilter=True), the same lists
-        bit for bit; the re-ranked and sharded paths do not take it."""
+        bit for bit; the re-ranked and sharded paths do not take it.
+        g_attrs / q_filter (ItemAttrs of the gallery rows, QueryFilter of the query rows): the
+        single-process Euclidean lists through search(g_attrs=, q_filter=), e.g.
+        q_filter=QueryFilter(cam_mask=cross_camera_mask(q_camids)) with g_attrs=ItemAttrs(camids=g_camids)
+        for cross-camera-only lists; the re-ranked and sharded paths refuse a filter."""
         from . import distributed as rd
         self._check_expansion()
+        if (g_attrs is not None or q_filter is not None) and (self.sharded or self.reranking):
+            raise _lib.ReidmiError("R1_mAP_eval.rank_lists: g_attrs / q_filter go with the single-process Euclidean "
+                                   "lists only (not sharded=True or reranking=True)")
         feats = torch.cat(self.feats, dim=0)
         if self.feat_norm:
             feats = l2_normalize_device(feats)
@@ -1320,7 +1543,7 @@ class R1_mAP_eval():
             if self.reranking:
                 from .reranking import re_ranking_search
                 return re_ranking_search(feats[:nq], feats[nq:], k, 50, 15, 0.3, *lab)
-            return search(feats[:nq], feats[nq:], k, *lab, prefilter=prefilter)
+            return search(feats[:nq], feats[nq:], k, *lab, prefilter=prefilter, g_attrs=g_attrs, q_filter=q_filter)
 
     def pair_stats(self, edges=None):
         """pair_stats (numpy) of the query rows against the gallery rows on the features and labels
